@@ -20,6 +20,19 @@ already sit on their range owners (no data-path collective); `value_offset_shard
 OFFSET-sharded start (rank r holds the r-th contiguous chunk of each sorted set: the slices arrive in value order and are
 not merged); `exchange` is one bare all-to-all-v.  --scaling weak (default):
 --set-size k-mers per set PER GPU; --scaling strong: in total (the metric's wording).
+
+A plain run does only what the headline needs: generate the sets, warm up, time --steps steps, write the outputs
+(--dump-outputs DIR) and print the line.  --full adds every other leg: the device generator checked against numpy, the
+full-size parity properties of the warm-up outputs, the taxid variant, the CPU baselines and, at N > 1, the
+offset-sharded / pipelined / C-ABI exchange legs and the bare all-to-all-v.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's union and intersection at N = 1 or with
+--no-exchange, every rank's from the end-to-end leg at N > 1; files suffixed _r<rank> when N > 1) as float64 .npy
+files: the codes split into their exact high / low 32-bit halves (union_hi, union_lo, inter_hi, inter_lo) at the
+positions union_index / inter_index -- every position when the output has at most DUMP_SAMPLE records, else one
+seeded position in each of DUMP_SAMPLE equal strata --, counts = [|union|, |inter|] and xor = the XOR checksum of
+each WHOLE output as [union_hi, union_lo, inter_hi, inter_lo].  The inputs are seeded, so the same arguments give
+the same files on a correct build.
 """
 import argparse
 import json
@@ -169,6 +182,38 @@ def check_outputs(A, B, U, I, window=1_000_000):
             assert start == a0 + b0 - lower(other, lo), "window at %d sits at the wrong rank" % start
 
 
+DUMP_SAMPLE = 1 << 20   # records per output and GPU: 3 float64 arrays per output, 48 MiB for both at N = 1
+
+
+def dump_outputs(dirname, U, I, rank, world):
+    """Writes the union U and intersection I (int64 device tensors of k=31 codes) as float64 .npy files (module docstring)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "_r%d" % rank if world > 1 else ""
+    per = max(1, DUMP_SAMPLE // world)
+    rng = np.random.default_rng(SEED + rank)
+
+    def save(name, arr):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.asarray(arr, dtype=np.float64))
+    xor = []
+    for name, t in (("union", U), ("inter", I)):
+        n = t.numel()
+        if n <= per:
+            pos = np.arange(n, dtype=np.int64)
+        else:
+            lo = np.arange(per, dtype=np.int64) * n // per
+            hi = (np.arange(per, dtype=np.int64) + 1) * n // per
+            pos = lo + rng.integers(0, hi - lo)
+        v = t[torch.from_numpy(pos).to(t.device)].cpu().numpy().view(np.uint64)
+        save(name + "_index", pos)
+        save(name + "_hi", v >> np.uint64(32))
+        save(name + "_lo", v & np.uint64(0xFFFFFFFF))
+        x = _xor_fold(t) & M64
+        xor += [x >> 32, x & 0xFFFFFFFF]
+    save("counts", [U.numel(), I.numel()])
+    save("xor", xor)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -178,10 +223,17 @@ def main():
                     help="k-mers per set: per GPU with --scaling weak, in total with --scaling strong")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = --set-size k-mers per set PER GPU (default); strong = in total (what the metric words)")
-    ap.add_argument("--cpu-sample", type=float, default=2e7, help="k-mers per set for the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=float, default=2e7, help="k-mers per set for the CPU baseline (0 = skip; --full only)")
     ap.add_argument("--no-exchange", action="store_true",
                     help="N > 1: skip the end-to-end leg; `value` is then the pre-partitioned figure (and says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and legs outside the headline: generator and parity checks, taxid variant, "
+                         "CPU baselines, the other exchange legs at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -223,11 +275,12 @@ def main():
     A, B = gen_sets_device(n_universe, gap_bits, base, SEED + 7919 * rank, dev)
     na, nb = A.numel(), B.numel()
 
-    # verify the device generator against numpy on a 1e6 sub-sample (rank's own seed/base)
-    An, Bn = gen_sets_numpy(min(1_000_000, n_universe), gap_bits, base, SEED + 7919 * rank)
-    ma, mb = min(na, len(An)), min(nb, len(Bn))
-    assert np.array_equal(A[:ma].cpu().numpy().view(np.uint64), An[:ma]), "device generator != numpy generator"
-    assert np.array_equal(B[:mb].cpu().numpy().view(np.uint64), Bn[:mb]), "device generator != numpy generator"
+    if args.full:
+        # verify the device generator against numpy on a 1e6 sub-sample (rank's own seed/base)
+        An, Bn = gen_sets_numpy(min(1_000_000, n_universe), gap_bits, base, SEED + 7919 * rank)
+        ma, mb = min(na, len(An)), min(nb, len(Bn))
+        assert np.array_equal(A[:ma].cpu().numpy().view(np.uint64), An[:ma]), "device generator != numpy generator"
+        assert np.array_equal(B[:mb].cpu().numpy().view(np.uint64), Bn[:mb]), "device generator != numpy generator"
 
     # output buffers are resident (first-touched) before anything is timed, like the inputs
     out_u = torch.zeros(na + nb, dtype=torch.int64, device=dev)
@@ -264,8 +317,9 @@ def main():
     # ---- the single-GPU path on this rank's prefix range (N = 1: the whole job) -------------------------------
     for _ in range(max(1, args.warmup)):
         nu, ni, _, _ = step()
-    check_outputs(A, B, out_u[:nu], out_i[:ni])   # full-size parity properties, once, outside the timed region
-    step()  # untimed: the check's multi-GB temporaries have just been freed; the first step behind them runs ~10 % slow
+    if args.full:
+        check_outputs(A, B, out_u[:nu], out_i[:ni])   # full-size parity properties, once, outside the timed region
+        step()  # untimed: the check's multi-GB temporaries have just been freed; the first step behind them runs ~10 % slow
     barrier()
     t0 = time.perf_counter()
     ku_sum = ki_sum = 0.0
@@ -278,6 +332,10 @@ def main():
     tot_in, tot_u, tot_i = sum_over_ranks([na + nb, nu, ni])
     ms_pre = dt * 1e3 / args.steps
     value_pre = 2.0 * tot_in * args.steps / dt  # each op consumes |A|+|B| input k-mers
+    dumped = False
+    if args.dump_outputs and (world == 1 or args.no_exchange):     # at N > 1 the headline is the end-to-end leg below
+        dump_outputs(args.dump_outputs, out_u[:nu], out_i[:ni], rank, world)
+        dumped = True
 
     # ---- taxid variant (OUTSIDE the timed region; rank 0): the same two sets with taxids, so that a driver-run number exists
     # for the paths north_star names ("with per-k-mer TaxId LCA reduction").  (a) per-RECORD taxids, SURVEY 8(d)'s generator:
@@ -285,7 +343,7 @@ def main():
     # case, every match is an LCA of two unrelated leaves); (b) ONE taxid per file (the reference's documented workflow:
     # `count -t`, the .unik header's global taxid) handed over as a scalar (ukm_setop2_ft).  Kernel ms by hipEvents.
     taxid_variant = None
-    if rank == 0 and os.environ.get("UKM_BENCH_NO_TAXID") != "1":
+    if args.full and rank == 0 and os.environ.get("UKM_BENCH_NO_TAXID") != "1":
         try:
             T = sum(8 ** d for d in range(8))
             child = np.arange(1, T + 1, dtype=np.uint32)
@@ -391,7 +449,7 @@ def main():
                           "algorithmic_bytes": bytes_i, "kernel_ms": ki * 1e3,
                           "read_only_achieved": 8 * (na + nb) / ki / 1e9, "read_only_frac": 8 * (na + nb) / ki / 1e9 / peak}
         cpu = None
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             cpu = cpu_baseline((4 * int(args.cpu_sample) + 2) // 3, 32)
         res = {
             "metric": "k-mers/sec for union+inter of 1e9-k-mer k=31 sets",
@@ -407,7 +465,8 @@ def main():
             "union_kmers_per_s_kernel": (na + nb) / ku, "inter_kmers_per_s_kernel": (na + nb) / ki,
             "value_prepartitioned": value_pre, "ms_per_step_prepartitioned": ms_pre,
             "parity_checked": "inclusion-exclusion, strict order, XOR checksum of checksums, 6 numpy-checked windows of 1e6 "
-                              "records with their ranks (warm-up outputs, full size)",
+                              "records with their ranks (warm-up outputs, full size)" if args.full else None,
+            "full": args.full,
         }
     # The leg below talks to the other ranks.  If one of them fails there (out of memory, an RCCL error) the
     # others would wait in a collective for ever and the numbers measured above would be lost with them: a
@@ -472,117 +531,122 @@ def main():
                     "ms_per_step": t1 * 1e3 / args.steps,
                     "note": "file-sharded start -> cut at the prefix splitters -> one all-to-all-v per input set -> k-way merge "
                             "of the received slices -> union + inter on the rank's range (each input is exchanged once per step)"}
-            # The same job from an OFFSET-sharded start (rank r holds the r-th contiguous chunk of each globally sorted
-            # set: what a rank has after reading its share of one sorted file, SURVEY 8(e)'s example).  The slices that
-            # arrive are already in value order, so dist.redistribute hands back the receive buffer and no merge pass
-            # runs; with uniform synthetic codes nearly everything already sits on its range owner, so this leg shows the
-            # floor of the end-to-end step (cuts + a near-empty all-to-all-v + union + inter).
-            try:
-                def offset_shard(X):
-                    sizes = [0] * world
-                    sizes[rank] = X.numel()
-                    tot = sum_over_ranks(sizes)                     # every rank's range size
-                    first, N = sum(tot[:rank]), sum(tot)
-                    counts = []
-                    for r in range(world):                          # records of mine inside chunk r = [r N / W, (r + 1) N / W)
-                        lo_r, hi_r = r * N // world, (r + 1) * N // world
-                        counts.append(max(0, min(hi_r, first + X.numel()) - max(lo_r, first)))
-                    full, _, _ = ud.exchange_sorted(X, counts)
-                    return full
-                Ao, Bo = offset_shard(A), offset_shard(B)
-
-                def step_off():
-                    (Al, Bl), _ = ud.redistribute(ctx, [Ao, Bo], 62)
-                    u = ctx.setop2(lib.OP_UNION, Al, Bl, out=out_u)
-                    i = ctx.setop2(lib.OP_INTER, Al, Bl, out=out_i)
-                    return Al, Bl, u, i
-                Al, Bl, ou, oi = step_off()
-                assert torch.equal(Al, A) and torch.equal(Bl, B), "offset-sharded redistribution did not rebuild the rank's range"
-                assert ou.numel() == nu and oi.numel() == ni
-                del Al, Bl
-                barrier()
-                t2 = time.perf_counter()
-                for _ in range(args.steps):
-                    step_off()
-                barrier()
-                t2 = max_over_ranks(time.perf_counter() - t2)
-                incl["offset_sharded_start"] = {
-                    "value": 2.0 * g_in * args.steps / t2, "unit": "k-mers/s", "ms_per_step": t2 * 1e3 / args.steps,
-                    "note": "rank r starts with the r-th contiguous chunk of each sorted set: the received slices are in "
-                            "value order and are used as they lie in the receive buffer (no merge pass)"}
-                del Ao, Bo
-            except Exception as e:
-                incl["offset_sharded_start"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            # The same step with each rank's range exchanged in FOUR sub-ranges by value: the rebuild of the slices that have
-            # arrived overlaps the transfer of the next sub-range (dist.redistribute_pipelined)
-            try:
-                def step_pipe():
-                    (Al, Bl), _ = ud.redistribute(ctx, [Af, Bf], 62, pipeline=4)
-                    u = ctx.setop2(lib.OP_UNION, Al, Bl, out=out_u)
-                    i = ctx.setop2(lib.OP_INTER, Al, Bl, out=out_i)
-                    return Al, Bl, u, i
-                Al, Bl, pu, pi = step_pipe()
-                assert torch.equal(Al, A) and torch.equal(Bl, B), "pipelined redistribution did not rebuild the rank's range"
-                assert pu.numel() == nu and pi.numel() == ni
-                del Al, Bl
-                barrier()
-                t4 = time.perf_counter()
-                for _ in range(args.steps):
-                    step_pipe()
-                barrier()
-                t4 = max_over_ranks(time.perf_counter() - t4)
-                incl["pipelined_4_subranges"] = {
-                    "value": 2.0 * g_in * args.steps / t4, "unit": "k-mers/s", "ms_per_step": t4 * 1e3 / args.steps,
-                    "note": "the end-to-end step with every input exchanged sub-range by sub-range (4 per rank): transfers overlap rebuilds"}
-            except Exception as e:
-                incl["pipelined_4_subranges"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            # The same end-to-end step through the LIBRARY'S OWN exchange -- ukm_comm_init + ukm_shard_counts +
-            # ukm_shard_exchange_known (grouped ncclSend / ncclRecv in ukm_comm.hip), the calls INTEGRATION.md's Go host
-            # makes; torch.distributed only hands the communicator id over.  RCCL wants one device per rank, so the 1-GPU
-            # test hook skips it.
-            if one_gpu:
-                incl["exchange_cabi"] = {"skipped": "UKM_BENCH_ONE_GPU: RCCL does not take two ranks on one device"}
-            else:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, eu, ei, rank, world)
+                dumped = True
+            if args.full:
+                # The same job from an OFFSET-sharded start (rank r holds the r-th contiguous chunk of each globally sorted
+                # set: what a rank has after reading its share of one sorted file, SURVEY 8(e)'s example).  The slices that
+                # arrive are already in value order, so dist.redistribute hands back the receive buffer and no merge pass
+                # runs; with uniform synthetic codes nearly everything already sits on its range owner, so this leg shows the
+                # floor of the end-to-end step (cuts + a near-empty all-to-all-v + union + inter).
                 try:
-                    ud.comm_init_from_dist(ctx)
+                    def offset_shard(X):
+                        sizes = [0] * world
+                        sizes[rank] = X.numel()
+                        tot = sum_over_ranks(sizes)                     # every rank's range size
+                        first, N = sum(tot[:rank]), sum(tot)
+                        counts = []
+                        for r in range(world):                          # records of mine inside chunk r = [r N / W, (r + 1) N / W)
+                            lo_r, hi_r = r * N // world, (r + 1) * N // world
+                            counts.append(max(0, min(hi_r, first + X.numel()) - max(lo_r, first)))
+                        full, _, _ = ud.exchange_sorted(X, counts)
+                        return full
+                    Ao, Bo = offset_shard(A), offset_shard(B)
 
-                    def step_cabi():
-                        (Al, Bl), _ = ud.redistribute_cabi(ctx, [Af, Bf], 62)
+                    def step_off():
+                        (Al, Bl), _ = ud.redistribute(ctx, [Ao, Bo], 62)
                         u = ctx.setop2(lib.OP_UNION, Al, Bl, out=out_u)
                         i = ctx.setop2(lib.OP_INTER, Al, Bl, out=out_i)
                         return Al, Bl, u, i
-                    Al, Bl, cu, ci = step_cabi()
-                    assert torch.equal(Al, A) and torch.equal(Bl, B), "C-ABI redistribution did not rebuild the rank's range"
-                    assert cu.numel() == nu and ci.numel() == ni
+                    Al, Bl, ou, oi = step_off()
+                    assert torch.equal(Al, A) and torch.equal(Bl, B), "offset-sharded redistribution did not rebuild the rank's range"
+                    assert ou.numel() == nu and oi.numel() == ni
                     del Al, Bl
                     barrier()
-                    t3 = time.perf_counter()
+                    t2 = time.perf_counter()
                     for _ in range(args.steps):
-                        step_cabi()
+                        step_off()
                     barrier()
-                    t3 = max_over_ranks(time.perf_counter() - t3)
-                    incl["exchange_cabi"] = {
-                        "value": 2.0 * g_in * args.steps / t3, "unit": "k-mers/s", "ms_per_step": t3 * 1e3 / args.steps,
-                        "note": "the end-to-end step with the exchange behind the C ABI (ukm_shard_counts + "
-                                "ukm_shard_exchange_known per set, ukm_merge_k of the received slices): what a Go host runs"}
-                    ctx.comm_destroy()
+                    t2 = max_over_ranks(time.perf_counter() - t2)
+                    incl["offset_sharded_start"] = {
+                        "value": 2.0 * g_in * args.steps / t2, "unit": "k-mers/s", "ms_per_step": t2 * 1e3 / args.steps,
+                        "note": "rank r starts with the r-th contiguous chunk of each sorted set: the received slices are in "
+                                "value order and are used as they lie in the receive buffer (no merge pass)"}
+                    del Ao, Bo
                 except Exception as e:
-                    incl["exchange_cabi"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            # the bare all-to-all-v of one set, for the link rate
-            counts = ud.cuts_to_counts(ctx.partition_points(Af, spl), Af.numel())
-            barrier()
-            te = time.perf_counter()
-            reps = 3
-            for _ in range(reps):
-                got, _, _ = ud.exchange_sorted(Af, counts)
-            barrier()
-            te = max_over_ranks((time.perf_counter() - te) / reps)
-            moved = Af.numel() - counts[rank]
-            exchange = {"ms": te * 1e3, "records_per_rank": int(Af.numel()), "bytes_sent_per_rank": int(moved) * 8,
-                        "GBps_per_rank": int(moved) * 8 / te / 1e9,
-                        "note": "one all-to-all-v (RCCL) redistributing one file-sharded set of ~n codes per rank "
-                                "to its prefix owners"}
-            del got, Af, Bf
+                    incl["offset_sharded_start"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                # The same step with each rank's range exchanged in FOUR sub-ranges by value: the rebuild of the slices that have
+                # arrived overlaps the transfer of the next sub-range (dist.redistribute_pipelined)
+                try:
+                    def step_pipe():
+                        (Al, Bl), _ = ud.redistribute(ctx, [Af, Bf], 62, pipeline=4)
+                        u = ctx.setop2(lib.OP_UNION, Al, Bl, out=out_u)
+                        i = ctx.setop2(lib.OP_INTER, Al, Bl, out=out_i)
+                        return Al, Bl, u, i
+                    Al, Bl, pu, pi = step_pipe()
+                    assert torch.equal(Al, A) and torch.equal(Bl, B), "pipelined redistribution did not rebuild the rank's range"
+                    assert pu.numel() == nu and pi.numel() == ni
+                    del Al, Bl
+                    barrier()
+                    t4 = time.perf_counter()
+                    for _ in range(args.steps):
+                        step_pipe()
+                    barrier()
+                    t4 = max_over_ranks(time.perf_counter() - t4)
+                    incl["pipelined_4_subranges"] = {
+                        "value": 2.0 * g_in * args.steps / t4, "unit": "k-mers/s", "ms_per_step": t4 * 1e3 / args.steps,
+                        "note": "the end-to-end step with every input exchanged sub-range by sub-range (4 per rank): transfers overlap rebuilds"}
+                except Exception as e:
+                    incl["pipelined_4_subranges"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                # The same end-to-end step through the LIBRARY'S OWN exchange -- ukm_comm_init + ukm_shard_counts +
+                # ukm_shard_exchange_known (grouped ncclSend / ncclRecv in ukm_comm.hip), the calls INTEGRATION.md's Go host
+                # makes; torch.distributed only hands the communicator id over.  RCCL wants one device per rank, so the 1-GPU
+                # test hook skips it.
+                if one_gpu:
+                    incl["exchange_cabi"] = {"skipped": "UKM_BENCH_ONE_GPU: RCCL does not take two ranks on one device"}
+                else:
+                    try:
+                        ud.comm_init_from_dist(ctx)
+
+                        def step_cabi():
+                            (Al, Bl), _ = ud.redistribute_cabi(ctx, [Af, Bf], 62)
+                            u = ctx.setop2(lib.OP_UNION, Al, Bl, out=out_u)
+                            i = ctx.setop2(lib.OP_INTER, Al, Bl, out=out_i)
+                            return Al, Bl, u, i
+                        Al, Bl, cu, ci = step_cabi()
+                        assert torch.equal(Al, A) and torch.equal(Bl, B), "C-ABI redistribution did not rebuild the rank's range"
+                        assert cu.numel() == nu and ci.numel() == ni
+                        del Al, Bl
+                        barrier()
+                        t3 = time.perf_counter()
+                        for _ in range(args.steps):
+                            step_cabi()
+                        barrier()
+                        t3 = max_over_ranks(time.perf_counter() - t3)
+                        incl["exchange_cabi"] = {
+                            "value": 2.0 * g_in * args.steps / t3, "unit": "k-mers/s", "ms_per_step": t3 * 1e3 / args.steps,
+                            "note": "the end-to-end step with the exchange behind the C ABI (ukm_shard_counts + "
+                                    "ukm_shard_exchange_known per set, ukm_merge_k of the received slices): what a Go host runs"}
+                        ctx.comm_destroy()
+                    except Exception as e:
+                        incl["exchange_cabi"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                # the bare all-to-all-v of one set, for the link rate
+                counts = ud.cuts_to_counts(ctx.partition_points(Af, spl), Af.numel())
+                barrier()
+                te = time.perf_counter()
+                reps = 3
+                for _ in range(reps):
+                    got, _, _ = ud.exchange_sorted(Af, counts)
+                barrier()
+                te = max_over_ranks((time.perf_counter() - te) / reps)
+                moved = Af.numel() - counts[rank]
+                exchange = {"ms": te * 1e3, "records_per_rank": int(Af.numel()), "bytes_sent_per_rank": int(moved) * 8,
+                            "GBps_per_rank": int(moved) * 8 / te / 1e9,
+                            "note": "one all-to-all-v (RCCL) redistributing one file-sharded set of ~n codes per rank "
+                                    "to its prefix owners"}
+                del got
+            del Af, Bf
         except Exception as e:  # the pre-partitioned numbers above never depend on this leg
             exchange = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
 
@@ -590,6 +654,7 @@ def main():
     if watchdog is not None:
         watchdog.cancel()
     if rank == 0:
+        res["outputs_dumped_to"] = args.dump_outputs if dumped else None
         if exchange:
             res["exchange"] = exchange
         if world > 1:

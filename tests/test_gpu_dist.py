@@ -193,7 +193,7 @@ def test_sampled_splitters_two_ranks_real_context(tmp_path):
     assert load("sampled").max() / load("sampled").mean() < 1.10
 
 
-def _run_bench_two_ranks(extra, world=2):
+def _run_bench_two_ranks(extra, world=2, full=True):
     import json
     import subprocess
     import sys
@@ -201,7 +201,7 @@ def _run_bench_two_ranks(extra, world=2):
     env = dict(os.environ, UKM_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--set-size", "1e6", "--cpu-sample", "0"] + extra
+           "--set-size", "1e6", "--cpu-sample", "0"] + (["--full"] if full else []) + extra
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -234,6 +234,26 @@ def test_bench_two_ranks_incl_exchange():
     assert res["config"]["global_set_size"] == 2_000_000
     assert res["roofline"]["frac"] > 0 and res["cpu_baseline"] is None
     assert res["roofline"]["traffic"] is None or res["roofline"]["traffic_from_profile"]["note"].startswith("profile-derived")
+
+
+def test_bench_two_ranks_plain_run_dumps_every_ranks_range(tmp_path):
+    """A plain run at N > 1 (no --full) times the end-to-end leg alone, and --dump-outputs writes each rank's union and
+    intersection from its last timed step: together they are the union and intersection of the two global sets."""
+    import bench
+    res = _run_bench_two_ranks(["--dump-outputs", str(tmp_path)], full=False)
+    assert res["value"] == res["value_incl_exchange"] and res["value_is"].startswith("end to end")
+    assert res["full"] is False and "exchange" not in res and "offset_sharded_start" not in res["incl_exchange"]
+    assert res["outputs_dumped_to"] == str(tmp_path)
+    n_universe = (4 * 1_000_000 + 2) // 3
+    for rank in range(2):
+        A, B = bench.gen_sets_numpy(n_universe, 31, rank * ((1 << 62) // 2), bench.SEED + 7919 * rank)
+        for name, want in (("union", np.union1d(A, B)), ("inter", np.intersect1d(A, B))):
+            got = lambda part: np.load(str(tmp_path / ("%s_%s_r%d.npy" % (name, part, rank))))
+            pos = got("index").astype(np.int64)
+            codes = (got("hi").astype(np.uint64) << np.uint64(32)) | got("lo").astype(np.uint64)
+            assert got("hi").dtype == np.float64 and np.array_equal(codes, want[pos])
+        counts = np.load(str(tmp_path / ("counts_r%d.npy" % rank)))
+        assert counts.tolist() == [len(np.union1d(A, B)), len(np.intersect1d(A, B))]
 
 
 def test_bench_eight_ranks_replay_of_the_drivers_launch_line():

@@ -7,7 +7,7 @@ TAG=${1:-r01}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 5 --warmup 2 --cpu-sample 0"
+CMD="python $R/bench.py --full --steps 5 --warmup 2 --cpu-sample 0"
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- $CMD > $O/trace.log 2>&1
 # (the PMC passes leave the taxid variant out -- UKM_BENCH_NO_TAXID=1: it lies outside the timed region and only adds launches
 #  of OTHER kernels; the kernel-trace pass above runs the default command as it is)
