@@ -107,11 +107,16 @@ int ukm_copy_sync(ukm_ctx *ctx);
  * records none) and (b) around all device work of the call */
 int ukm_last_kernel_ms(ukm_ctx *ctx, float *ms);
 int ukm_last_call_ms(ukm_ctx *ctx, float *ms);
-/* diagnostic: which internal route answered the most recent n-way call (ukm_union / ukm_merge_k / ukm_common):
- * 0 none / 2-way only, 1 pairwise tree of 2-way kernels, 2 multi-level k-way streaming merge, 3 LDS hash-probe union,
- * 4 single-pass range merge (one LDS tile per value range), 5 the same pass counting the records of every code
- * (ukm_common below the number of files), 6 ukm_common / ukm_merge_k -d by counting hash probes, 7 keep-everything merge
- * by placement (counts per code, runs written in one piece).  Tests use it to see that a knob took effect. */
+/* diagnostic: which internal route answered the most recent n-way call (ukm_union / ukm_merge_k / ukm_common), one of
+ * UKM_ROUTE_*.  Tests use it to see that a knob took effect. */
+#define UKM_ROUTE_NONE 0     /* none / 2-way only */
+#define UKM_ROUTE_TREE 1     /* pairwise tree of 2-way kernels */
+#define UKM_ROUTE_KWAY 2     /* multi-level k-way streaming merge */
+#define UKM_ROUTE_PUNION 3   /* LDS hash-probe union */
+#define UKM_ROUTE_SRMERGE 4  /* single-pass range merge (one LDS tile per value range) */
+#define UKM_ROUTE_SRCOMMON 5 /* the same pass counting the records of every code (ukm_common below the number of files) */
+#define UKM_ROUTE_PCOMMON 6  /* ukm_common / ukm_merge_k -d by counting hash probes */
+#define UKM_ROUTE_PLACE 7    /* keep-everything merge by placement (counts per code, runs written in one piece) */
 int ukm_last_route(ukm_ctx *ctx);
 
 /* ---- route policy as API (round 5).  The n-way entry points choose between several internal routes (ukm_last_route) by

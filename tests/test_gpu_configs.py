@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import splitmix64, synth_tree
+from unikmer_amd.lib import ROUTE_PCOMMON, ROUTE_PUNION
 
 pytestmark = pytest.mark.gpu
 
@@ -315,7 +316,7 @@ def test_probe_union_pipelined_steps_and_order_check(env, monkeypatch):
     later.append(np.unique(rng.integers(1, int(U[-1]), 700).astype(np.uint64)))
     files = base + later
     assert np.array_equal(ctx.union(files), O.union(files))
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     # one swapped neighbouring pair: every position class of a 900-record later file
     victim = np.sort(rng.choice(U, 900, replace=False)).astype(np.uint64)
     b1 = int(np.searchsorted(victim, cut1))               # first record of the second range's slice
@@ -327,10 +328,10 @@ def test_probe_union_pipelined_steps_and_order_check(env, monkeypatch):
         v[sp], v[sp + 1] = v[sp + 1], v[sp]
         trial = base + [later[3], v, later[10]]
         assert np.array_equal(ctx.union(trial), O.union(trial)), sp
-        assert ctx.last_route() != 3, sp                   # the probe pass saw the inversion and backed out
+        assert ctx.last_route() != ROUTE_PUNION, sp                   # the probe pass saw the inversion and backed out
     clean = base + [later[3], victim, later[10]]
     assert np.array_equal(ctx.union(clean), O.union(clean))
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
 
 
 def test_probe_union_matches_oracle(env, monkeypatch):
@@ -350,7 +351,7 @@ def test_probe_union_matches_oracle(env, monkeypatch):
         U = _universe(n_univ)
         files = [U[_member(len(U), f, p, 77)] for f in range(nfiles)]
         assert np.array_equal(ctx.union(files), O.union(files)), (n_univ, nfiles, p)
-        assert ctx.last_route() == 3, (n_univ, nfiles, p)
+        assert ctx.last_route() == ROUTE_PUNION, (n_univ, nfiles, p)
     # later files with private codes (misses), duplicates inside files, all-ones hashes
     U = _universe(50_000, gap_bits=40)
     files = [U[_member(len(U), f, 0.6, 5)] for f in range(30)]
@@ -396,11 +397,11 @@ def test_probe_union_matches_oracle(env, monkeypatch):
     taxs = [_taxids(f, T, i) for i, f in enumerate(files)]
     ok, ot = O.union(files, taxs, tax)
     gk, gt = ctx.union(files, taxs)
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     monkeypatch.setenv("UKM_PUNION_TAX", "0")
     gk, gt = ctx.union(files, taxs)
-    assert ctx.last_route() != 3
+    assert ctx.last_route() != ROUTE_PUNION
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
 
 
@@ -424,7 +425,7 @@ def test_probe_union_with_taxids_matches_oracle(env, monkeypatch):
             else:
                 taxs = [_taxids(f, T, i) if i % 3 else None for i, f in enumerate(files)]
             gk, gt = ctx.union(files, taxs)
-            assert ctx.last_route() == 3, (n_univ, nfiles, kind)
+            assert ctx.last_route() == ROUTE_PUNION, (n_univ, nfiles, kind)
             ok, ot = O.union(files, taxs, tax)
             assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (n_univ, nfiles, kind)
     # tiny files in front (a plasmid before the genomes): the base set is built from the LARGEST files
@@ -433,9 +434,9 @@ def test_probe_union_with_taxids_matches_oracle(env, monkeypatch):
     for i in (0, 1, 2, 5):
         files[i] = files[i][:7 + i]
     taxs = [_taxids(f, T, i) for i, f in enumerate(files)]
-    assert np.array_equal(ctx.union(files), O.union(files)) and ctx.last_route() == 3
+    assert np.array_equal(ctx.union(files), O.union(files)) and ctx.last_route() == ROUTE_PUNION
     gk, gt = ctx.union(files, taxs)
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     ok, ot = O.union(files, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     # later files with private codes, duplicates inside files (their taxids differ), all-ones hashes
@@ -451,7 +452,7 @@ def test_probe_union_with_taxids_matches_oracle(env, monkeypatch):
     for mode in ("1", "2"):
         monkeypatch.setenv("UKM_PUNION", mode)
         gk, gt = ctx.union(files, taxs)
-        assert ctx.last_route() == 3
+        assert ctx.last_route() == ROUTE_PUNION
         assert np.array_equal(gk, ok) and np.array_equal(gt, ot), mode
     # thousands of new codes per range: past the table's share the rest is listed record by record
     Us = _universe(5_000, gap_bits=30)
@@ -461,7 +462,7 @@ def test_probe_union_with_taxids_matches_oracle(env, monkeypatch):
                        for f in range(22)]
     taxs = [(1 + rng.integers(0, T, len(f))).astype(np.uint32) for f in crowded]
     gk, gt = ctx.union(crowded, taxs)
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     ok, ot = O.union(crowded, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     # disjoint files (every record a miss) and an unsorted later file
@@ -475,7 +476,7 @@ def test_probe_union_with_taxids_matches_oracle(env, monkeypatch):
     perm = rng.permutation(len(dirty[15]))
     dirty[15], taxs[15] = dirty[15][perm], taxs[15][perm]
     gk, gt = ctx.union(dirty, taxs)
-    assert ctx.last_route() != 3
+    assert ctx.last_route() != ROUTE_PUNION
     ok, ot = O.union(dirty, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
 
@@ -510,20 +511,20 @@ def test_common_by_counting_probes_matches_oracle(env, monkeypatch):
             # every file counted (the duplicates inside the first file too) -- the same tables with a threshold of two
             if taxs is None:
                 assert np.array_equal(ctx.merge_k(files, mode=L.REPEATED), O.merge_k(files, mode=O.REPEATED)), (n_univ, nfiles, kind)
-                assert ctx.last_route() == 6, (n_univ, nfiles, kind)
+                assert ctx.last_route() == ROUTE_PCOMMON, (n_univ, nfiles, kind)
             else:
                 gk, gt = ctx.merge_k(files, taxs, mode=L.REPEATED)
-                assert ctx.last_route() == 6, (n_univ, nfiles, kind)
+                assert ctx.last_route() == ROUTE_PCOMMON, (n_univ, nfiles, kind)
                 ok, ot = O.merge_k(files, taxs, mode=O.REPEATED, tax=tax)
                 assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (n_univ, nfiles, kind)
             for thr in (2, nfiles // 2, nfiles - 1, nfiles, nfiles + 1):
                 if taxs is None:
                     g = ctx.common(files, thr)
-                    assert ctx.last_route() == 6, (n_univ, nfiles, kind, thr)
+                    assert ctx.last_route() == ROUTE_PCOMMON, (n_univ, nfiles, kind, thr)
                     assert np.array_equal(g, O.common(files, thr)), (n_univ, nfiles, kind, thr)
                 else:
                     gk, gt = ctx.common(files, thr, taxs)
-                    assert ctx.last_route() == 6, (n_univ, nfiles, kind, thr)
+                    assert ctx.last_route() == ROUTE_PCOMMON, (n_univ, nfiles, kind, thr)
                     ok, ot = O.common(files, thr, taxs, tax)
                     assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (n_univ, nfiles, kind, thr)
     # more new codes than a table claims, all-ones codes, an unsorted later file, files that share nothing: declined
@@ -544,13 +545,13 @@ def test_common_by_counting_probes_matches_oracle(env, monkeypatch):
     perm = rng.permutation(len(dirty[15]))
     dirty[15], dt[15] = dirty[15][perm], dt[15][perm]
     gk, gt = ctx.common(dirty, 20, dt)
-    assert ctx.last_route() != 6
+    assert ctx.last_route() != ROUTE_PCOMMON
     assert np.array_equal(gk, want[0]) and np.array_equal(gt, want[1])
     disjoint = [np.sort(rng.choice(1 << 40, 4000, replace=False).astype(np.uint64) + np.uint64(f << 44)) for f in range(26)]
-    assert len(ctx.common(disjoint, 2)) == 0 and ctx.last_route() != 6
+    assert len(ctx.common(disjoint, 2)) == 0 and ctx.last_route() != ROUTE_PCOMMON
     monkeypatch.setenv("UKM_PUNION", "0")
     gk, gt = ctx.common(files, 20, taxs)
-    assert ctx.last_route() != 6
+    assert ctx.last_route() != ROUTE_PCOMMON
     assert np.array_equal(gk, want[0]) and np.array_equal(gt, want[1])
 
 
@@ -596,12 +597,12 @@ def test_probe_union_taxid_fold_on_a_forest_with_merged_zero_and_unknown_ids(mon
                 t[i] = rng.integers(5000, 5121)           # one ternary tree
         taxs.append(t.astype(np.uint32))
     gk, gt = c.union(files, taxs)
-    assert c.last_route() == 3
+    assert c.last_route() == ROUTE_PUNION
     ok, ot = O.union(files, taxs, tax)
     assert len(ok) > 1000 and np.array_equal(gk, ok) and np.array_equal(gt, ot)
     taxs[40][7] = np.uint32(2**32 - 1)
     gk, gt = c.union(files, taxs)
-    assert c.last_route() != 3
+    assert c.last_route() != ROUTE_PUNION
     ok, ot = O.union(files, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     c.close()

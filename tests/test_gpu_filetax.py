@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import splitmix64, synth_tree
+from unikmer_amd.lib import ROUTE_KWAY, ROUTE_PLACE, ROUTE_PUNION, ROUTE_SRMERGE, ROUTE_TREE
 
 pytestmark = pytest.mark.gpu
 
@@ -240,8 +241,8 @@ def test_nway_file_taxids_quirks(env):
     _eq(ctx.union(sh, cts[:4]), O.union(sh, _expand(sh, cts[:4]), tax))
 
 
-@pytest.mark.parametrize("knob,value,route", [("UKM_PUNION", "2", 3), ("UKM_PUNION", "1", 3), ("UKM_SRMERGE", "1", 4), ("UKM_KWAY", "1", 2),
-                                              ("UKM_NO_KWAY", "1", 1), ("UKM_PUNION_RANKED", "0", 3)])
+@pytest.mark.parametrize("knob,value,route", [("UKM_PUNION", "2", ROUTE_PUNION), ("UKM_PUNION", "1", ROUTE_PUNION), ("UKM_SRMERGE", "1", ROUTE_SRMERGE),
+                                              ("UKM_KWAY", "1", ROUTE_KWAY), ("UKM_NO_KWAY", "1", ROUTE_TREE), ("UKM_PUNION_RANKED", "0", ROUTE_PUNION)])
 def test_union_file_taxids_every_route(env, monkeypatch, knob, value, route):
     """the n-file union with one taxid per file through the hash probes (the file's taxid and pre-order number as scalars),
     the single-pass merge, the k-way merge and the pairwise tree (the arrays are built on the device for the merges)"""
@@ -288,7 +289,7 @@ def test_probe_paths_file_taxids_new_codes_and_aliases(env, monkeypatch):
         taxs = [alias[(i + rep) % len(alias)] for i in range(nfiles)]
         ex = _expand(files, taxs)
         gk, gt = ctx.union(files, taxs)
-        assert ctx.last_route() == 3
+        assert ctx.last_route() == ROUTE_PUNION
         _eq((gk, gt), O.union(files, ex, tax), ("union alias", rep))
         _eq(ctx.union(files, ex), O.union(files, ex, tax), ("union alias arrays", rep))
         for thr in (2, nfiles // 2):
@@ -329,7 +330,7 @@ def test_probe_tables_clade_mode_per_record_taxids(env, monkeypatch, clade):
     for name, taxs in shapes.items():
         ex = _expand(files, taxs)
         gk, gt = ctx.union(files, taxs)
-        assert ctx.last_route() == 3, name
+        assert ctx.last_route() == ROUTE_PUNION, name
         _eq((gk, gt), O.union(files, ex, tax), ("union", name, clade))
         for thr in (2, nfiles // 2, nfiles - 1):
             _eq(ctx.common(files, thr, taxs), O.common(files, thr, ex, tax), ("common", name, thr, clade))
@@ -381,13 +382,13 @@ def test_clade_folds_on_a_skewed_taxonomy(monkeypatch):
     monkeypatch.setenv("UKM_PUNION", "2")
     monkeypatch.setenv("UKM_PUNION_CLADE", "1")
     _eq(ctx.union(files, taxs), O.union(files, taxs, tax), "probe union, clade mode")
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     _eq(ctx.common(files, nfiles // 2, taxs), O.common(files, nfiles // 2, taxs, tax), "counting probes, clade mode")
     monkeypatch.setenv("UKM_PUNION", "0")
     monkeypatch.setenv("UKM_SRMERGE", "1")
     monkeypatch.setenv("UKM_SRMERGE_CLADE", "1")
     _eq(ctx.union(files, taxs), O.union(files, taxs, tax), "single pass, clade emit")
-    assert ctx.last_route() == 4
+    assert ctx.last_route() == ROUTE_SRMERGE
     monkeypatch.delenv("UKM_SRMERGE", raising=False)
     core = _member(len(U), 0, 0.3, 277)
     cfiles = [U[core | _member(len(U), f + 1, 0.6, 278)] for f in range(nfiles)]
@@ -439,7 +440,7 @@ def test_merge_by_placement_with_file_taxids(env, monkeypatch):
         for mode in (L.PLAIN, L.UNIQUE, L.REPEATED):
             gk, gt = ctx.merge_k(files, taxs, mode=mode)
             if mode == L.PLAIN and name != "same":
-                assert ctx.last_route() == 7, (name, ctx.last_route())
+                assert ctx.last_route() == ROUTE_PLACE, (name, ctx.last_route())
             ok, ot = O.merge_k(files, ex, mode=mode, tax=tax)
             assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (name, mode)
 
@@ -463,7 +464,7 @@ def test_ranked_probe_union_step_edges(env, monkeypatch):
     files = base + later
     taxs = [int(pool[(5 * i + 3) % len(pool)]) for i in range(len(files))]
     _eq(ctx.union(files, taxs), O.union(files, _expand(files, taxs), tax))
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     victim = later[2]
     spots = sorted({0, 1, 2, 126, 127, 128, 129, 254, 255, 256, 257, len(victim) - 2, len(victim) - 3} |
                    set(int(x) for x in rng.integers(0, len(victim) - 1, 14)))
@@ -475,8 +476,8 @@ def test_ranked_probe_union_step_edges(env, monkeypatch):
         trial = list(small)
         trial[9] = v
         _eq(ctx.union(trial, tt), O.union(trial, _expand(trial, tt), tax), sp)
-        assert ctx.last_route() != 3, sp
+        assert ctx.last_route() != ROUTE_PUNION, sp
     trial = list(small)
     trial[9] = victim
     _eq(ctx.union(trial, tt), O.union(trial, _expand(trial, tt), tax))
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION

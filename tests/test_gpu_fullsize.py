@@ -14,6 +14,7 @@ import sys
 
 import numpy as np
 import pytest
+from unikmer_amd.lib import ROUTE_PCOMMON, ROUTE_PLACE, ROUTE_PUNION, ROUTE_SRCOMMON, ROUTE_SRMERGE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -270,7 +271,7 @@ def test_config3_union_with_taxids_full_size(env, monkeypatch):
     out = torch.empty(nu + 8, dtype=torch.int64, device=dev)
     outt = torch.empty(nu + 8, dtype=torch.int32, device=dev)
     gk, gt = ctx.union(files, taxs, out=out, out_taxids=outt)
-    assert ctx.last_route() == 3
+    assert ctx.last_route() == ROUTE_PUNION
     assert gk.numel() == expect_k.numel() and _strict(gk)
     assert bool((gk == expect_k).all()) and bool((gt == expect_t).all())
     del expect_k, expect_t, taxs
@@ -279,7 +280,7 @@ def test_config3_union_with_taxids_full_size(env, monkeypatch):
     taxs = [(1 + (bench.splitmix64_torch(k ^ bench._i64(bench.SEED + 2 + f)) & ((1 << 40) - 1)) % T).to(torch.int32)
             for f, k in enumerate(files)]
     gk, gt = ctx.union(files, taxs, out=out, out_taxids=outt)
-    assert ctx.last_route() == 3 and _strict(gk)
+    assert ctx.last_route() == ROUTE_PUNION and _strict(gk)
     Ws = 200_000
     for start in (0, gk.numel() // 2 - Ws // 2, gk.numel() - Ws):
         wk, wt = gk[start:start + Ws], gt[start:start + Ws]
@@ -517,16 +518,16 @@ def test_config4_inter_diff_common_1000_files_x_1e6_full_size(env, monkeypatch, 
         otc = torch.empty(total + 8, dtype=torch.int32, device=dev)
         monkeypatch.setenv("UKM_COMMON_PROBE", "0")
         same(ctx.common(files, nfiles, taxs, out=okc, out_taxids=otc), "common", "counting probes")
-        assert ctx.last_route() == 6   # (hash probes against the first file with a record count per entry, ukm_punion.hip)
+        assert ctx.last_route() == ROUTE_PCOMMON   # (hash probes against the first file with a record count per entry, ukm_punion.hip)
         monkeypatch.delenv("UKM_COMMON_PROBE")
         # one below the number of files: codes that one file lacks survive too
         same(ctx.common(files, nfiles - 1, taxs, out=okc, out_taxids=otc), "common_minus_1", "counting probes")
-        assert ctx.last_route() == 6
+        assert ctx.last_route() == ROUTE_PCOMMON
         assert len(want["common_minus_1"][0]) >= len(want["common"][0])
         # ... and through the single-pass merge counting inside its tiles (ukm_srmerge.hip)
         monkeypatch.setenv("UKM_PUNION", "0")
         same(ctx.common(files, nfiles - 1, taxs, out=okc, out_taxids=otc), "common_minus_1", "counted single pass")
-        assert ctx.last_route() == 5
+        assert ctx.last_route() == ROUTE_SRCOMMON
         monkeypatch.delenv("UKM_PUNION")
 
 
@@ -584,7 +585,7 @@ def test_default_routes_1000_files_x_1e6_full_size(env, monkeypatch):
         assert gk.numel() == len(wk), (name, gk.numel(), len(wk))
         assert np.array_equal(_np(gk), wk), name
         assert np.array_equal(gt.cpu().numpy().view(np.uint32), wt), name
-    for name, route in (("place", 7), ("single", 4)):
+    for name, route in (("place", ROUTE_PLACE), ("single", ROUTE_SRMERGE)):
         files, taxs = shapes[name]
         total = sum(x.numel() for x in files)
         assert 0.8e9 < total < 1.3e9
@@ -599,7 +600,7 @@ def test_default_routes_1000_files_x_1e6_full_size(env, monkeypatch):
     ok = torch.empty(10 * per + 8, dtype=torch.int64, device=dev)
     ot = torch.empty(10 * per + 8, dtype=torch.int32, device=dev)
     got = ctx.union(files, taxs, out=ok, out_taxids=ot)
-    assert ctx.last_route() == 3 and ctx.stat("punion_attempts") == 2, (ctx.last_route(), ctx.stat("punion_attempts"))
+    assert ctx.last_route() == ROUTE_PUNION and ctx.stat("punion_attempts") == 2, (ctx.last_route(), ctx.stat("punion_attempts"))
     same(got, "probe")
 
 

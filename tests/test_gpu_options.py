@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import splitmix64
+from unikmer_amd.lib import ROUTE_KWAY, ROUTE_PLACE, ROUTE_PUNION, ROUTE_TREE
 
 pytestmark = pytest.mark.gpu
 
@@ -32,29 +33,29 @@ def test_options_steer_routes_and_environment_is_read_once(monkeypatch):
         files = _files(30, 40_000, 0.5)
         exp = O.union(files)
         assert ctx.get_option("punion") == 1 and ctx.get_option("place") is None
-        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == 3
+        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == ROUTE_PUNION
         assert ctx.stat("punion_attempts") == 1
         # the environment changes AFTER the context exists: no effect on it
         monkeypatch.setenv("UKM_PUNION", "0")
-        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == 3
+        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == ROUTE_PUNION
         # an option set on the context wins over its defaults
         ctx.set_option("punion", 0)
-        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == 2
+        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == ROUTE_KWAY
         ctx.set_option("no_kway", 1)
-        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == 1
+        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == ROUTE_TREE
         ctx.set_option("no_kway", None)
         ctx.set_option("punion", None)
         assert ctx.get_option("punion") == 1           # back to what the environment said at creation
-        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == 3
+        assert np.array_equal(ctx.union(files), exp) and ctx.last_route() == ROUTE_PUNION
         # keep-everything merge: placement on demand
         ctx.set_option("place", 1)
         many = _files(100, 8_000, 0.8)
         got = ctx.merge_k(many, mode=L.PLAIN)
-        assert ctx.last_route() == 7 and np.array_equal(got, np.sort(np.concatenate(many)))
+        assert ctx.last_route() == ROUTE_PLACE and np.array_equal(got, np.sort(np.concatenate(many)))
         ctx.set_option("place", 0)
         ctx.set_option("srmerge", 0)
         got = ctx.merge_k(many, mode=L.PLAIN)
-        assert ctx.last_route() == 2 and np.array_equal(got, np.sort(np.concatenate(many)))
+        assert ctx.last_route() == ROUTE_KWAY and np.array_equal(got, np.sort(np.concatenate(many)))
         with pytest.raises(L.UkmError):
             ctx.set_option("no_such_option", 1)
         assert ctx.stat("workspace_bytes") > 0
@@ -64,7 +65,7 @@ def test_options_steer_routes_and_environment_is_read_once(monkeypatch):
     ctx2 = L.Context(0)
     try:
         assert ctx2.get_option("punion") == 0
-        assert np.array_equal(ctx2.union(files), exp) and ctx2.last_route() == 2
+        assert np.array_equal(ctx2.union(files), exp) and ctx2.last_route() == ROUTE_KWAY
     finally:
         ctx2.close()
 

@@ -4,16 +4,16 @@ from one probe pass, every code's run written in one piece, the TaxIds placed ei
 sort of the concatenation (= the heap's order: equal codes in file order) and the oracle's modes.
 
 UKM_PLACE=1 / UKM_PUNION=1 force the routes at test sizes (the library takes them from 96 files and 2^26 records on when a
-workgroup's slice of a file is long enough); `ctx.last_route() == 7` shows the placement answered."""
+workgroup's slice of a file is long enough); `ctx.last_route() == ROUTE_PLACE` shows the placement answered."""
 import numpy as np
 import pytest
 
 from conftest import splitmix64, synth_tree
+from unikmer_amd.lib import ROUTE_PLACE
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x756E696B6D6572
-ROUTE_PLACE = 7
 
 
 @pytest.fixture(scope="module")

@@ -5,18 +5,17 @@ fold (union.go:186-208) and `common` below the full threshold (common.go:220-344
 
 UKM_SRMERGE=1 forces the route at test sizes (the library takes it for records with taxids from 512 streams and 2^24
 records on);
-`ctx.last_route() == 4` shows it answered.  UKM_SRMERGE_FILL over-fills the value ranges so that every range needs
+`ctx.last_route() == ROUTE_SRMERGE` shows it answered.  UKM_SRMERGE_FILL over-fills the value ranges so that every range needs
 several passes by value (the quota rule)."""
 import numpy as np
 import pytest
 
 from conftest import splitmix64, synth_tree
+from unikmer_amd.lib import ROUTE_SRCOMMON, ROUTE_SRMERGE
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x756E696B6D6572
-ROUTE_SR = 4
-ROUTE_SR_COMMON = 5
 
 
 @pytest.fixture(scope="module")
@@ -81,23 +80,23 @@ def test_merge_modes_and_union_many_streams(env, monkeypatch, nfiles, per, p, bu
         monkeypatch.setenv("UKM_SRMERGE_BUCKETS", buckets)
     files, taxs = _shape(nfiles, per, p, T)
     gk, gt = ctx.merge_k(files, taxs, mode=L.PLAIN)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ek, et = _stable(files, taxs)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
     assert np.array_equal(ctx.merge_k(files, mode=L.PLAIN), ek)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     for mode in (L.UNIQUE, L.REPEATED):
         for final in (True, False):
             assert np.array_equal(ctx.merge_k(files, mode=mode, final_round=final),
                                   O.merge_k(files, mode=mode, final_round=final)), (mode, final)
-            assert ctx.last_route() == ROUTE_SR
+            assert ctx.last_route() == ROUTE_SRMERGE
             gk, gt = ctx.merge_k(files, taxs, mode=mode, final_round=final)
             ok, ot = O.merge_k(files, taxs, mode=mode, final_round=final, tax=tax)
             assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (mode, final)
     assert np.array_equal(ctx.union(files), O.union(files))
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     gk, gt = ctx.union(files, taxs)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ok, ot = O.union(files, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     thr = max(2, int(nfiles * p * 0.8))
@@ -107,7 +106,7 @@ def test_merge_modes_and_union_many_streams(env, monkeypatch, nfiles, per, p, bu
     # the multi-level merge gives the same (the route is a choice, not a semantic)
     monkeypatch.setenv("UKM_SRMERGE", "0")
     gk2, gt2 = ctx.merge_k(files, taxs, mode=L.PLAIN)
-    assert ctx.last_route() != ROUTE_SR
+    assert ctx.last_route() != ROUTE_SRMERGE
     assert np.array_equal(gk2, ek) and np.array_equal(gt2, et)
 
 
@@ -139,7 +138,7 @@ def test_union_emit_with_clade_codes(env, monkeypatch, nfiles, per, p, clade):
     shapes["zeros_and_unknown"] = holes
     for name, taxs in shapes.items():
         gk, gt = ctx.union(files, taxs)
-        assert ctx.last_route() == ROUTE_SR
+        assert ctx.last_route() == ROUTE_SRMERGE
         ok, ot = O.union(files, taxs, tax)
         assert np.array_equal(gk, ok) and np.array_equal(gt, ot), (name, clade)
         thr = max(2, int(len(files) * p * 0.8))
@@ -163,11 +162,11 @@ def test_ranges_that_do_not_fit_a_tile_are_worked_off_by_value(env, monkeypatch,
     streams = [np.sort(rng.integers(0, 1 << 20, 900 + 7 * i).astype(np.uint64)) for i in range(nfiles)]   # many ties, duplicates inside
     taxs = [_taxids(s + np.uint64(i), T, i) for i, s in enumerate(streams)]
     gk, gt = ctx.merge_k(streams, taxs, mode=L.PLAIN)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ek, et = _stable(streams, taxs)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
     gk, gt = ctx.union(streams, taxs)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ok, ot = O.union(streams, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     gk, gt = ctx.merge_k(streams, taxs, mode=L.REPEATED)
@@ -197,12 +196,12 @@ def test_uneven_streams_all_ones_codes_and_a_crowded_code(env, monkeypatch, orde
         streams.append(np.sort(s))
     taxs = [_taxids(s + np.uint64(i), T, i) for i, s in enumerate(streams)]
     gk, gt = ctx.merge_k(streams, taxs, mode=L.PLAIN)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ek, et = _stable(streams, taxs)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
     assert np.array_equal(ctx.merge_k(streams, mode=L.PLAIN), ek)
     gk, gt = ctx.union(streams, taxs)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ok, ot = O.union(streams, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     assert np.array_equal(ctx.union(streams), O.union(streams))
@@ -210,7 +209,7 @@ def test_uneven_streams_all_ones_codes_and_a_crowded_code(env, monkeypatch, orde
     streams2 = [np.sort(np.concatenate([s, np.full(40, crowd)])) for s in streams[:200]]
     taxs2 = [_taxids(s + np.uint64(i), T, i) for i, s in enumerate(streams2)]
     gk, gt = ctx.merge_k(streams2, taxs2, mode=L.PLAIN)
-    assert ctx.last_route() != ROUTE_SR
+    assert ctx.last_route() != ROUTE_SRMERGE
     ek, et = _stable(streams2, taxs2)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
     gk, gt = ctx.union(streams2, taxs2)
@@ -225,7 +224,7 @@ def test_unsorted_stream_sends_the_call_to_the_general_route(env, monkeypatch):
     streams = [np.sort(rng.integers(0, 1 << 40, 2000).astype(np.uint64)) for _ in range(120)]
     streams[77] = streams[77][::-1].copy()
     assert np.array_equal(ctx.merge_k(streams, mode=L.PLAIN), np.sort(np.concatenate(streams)))
-    assert ctx.last_route() != ROUTE_SR
+    assert ctx.last_route() != ROUTE_SRMERGE
     assert np.array_equal(ctx.union(streams), O.union(streams))
 
 
@@ -270,7 +269,7 @@ def test_union_taxid_fold_on_a_forest_with_merged_zero_and_unknown_ids(monkeypat
         t[tern] = rng.integers(5000, 5121, int(tern.sum()))
         taxs.append(t.astype(np.uint32))
     gk, gt = c.union(files, taxs)
-    assert c.last_route() == ROUTE_SR
+    assert c.last_route() == ROUTE_SRMERGE
     ok, ot = O.union(files, taxs, tax)
     assert len(ok) > 1000 and np.array_equal(gk, ok) and np.array_equal(gt, ot)
     gk, gt = c.merge_k(files, taxs, mode=L.REPEATED)
@@ -287,14 +286,14 @@ def test_default_choice_takes_the_route_for_many_streams(env):
     streams = [np.sort(rng.integers(0, 1 << 61, 30_000).astype(np.uint64)) for _ in range(600)]
     taxs = [_taxids(s + np.uint64(i), T, i) for i, s in enumerate(streams)]
     gk, gt = ctx.merge_k(streams, taxs, mode=L.PLAIN)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ek, et = _stable(streams, taxs)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
     g = ctx.merge_k(streams, mode=L.PLAIN)
-    assert ctx.last_route() != ROUTE_SR
+    assert ctx.last_route() != ROUTE_SRMERGE
     assert np.array_equal(g, ek)
     g = ctx.union(streams[:40])
-    assert ctx.last_route() != ROUTE_SR
+    assert ctx.last_route() != ROUTE_SRMERGE
     assert np.array_equal(g, O.union(streams[:40]))
 
 
@@ -309,11 +308,11 @@ def test_streams_without_taxids_among_streams_with_taxids(env, monkeypatch):
     files = [f for f in files if len(f)]
     taxs = [None if i % 7 == 3 else _taxids(f + np.uint64(i), T, i) for i, f in enumerate(files)]
     gk, gt = ctx.union(files, taxs)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     ok, ot = O.union(files, taxs, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     gk, gt = ctx.merge_k(files, taxs, mode=L.PLAIN)
-    assert ctx.last_route() == ROUTE_SR
+    assert ctx.last_route() == ROUTE_SRMERGE
     zt = [np.zeros(len(f), np.uint32) if t is None else t for f, t in zip(files, taxs)]
     ek, et = _stable(files, zt)
     assert np.array_equal(gk, ek) and np.array_equal(gt, et)
@@ -345,19 +344,19 @@ def test_common_below_the_number_of_files_counts_inside_the_tiles(env, monkeypat
     taxs = [_taxids(x + np.uint64(i), T, i) for i, x in enumerate(files)]
     for thr in (2, 3, 60, 150, 199, 200, 201, nfiles - 1, nfiles):
         g = ctx.common(files, thr)
-        assert ctx.last_route() == ROUTE_SR_COMMON, thr
+        assert ctx.last_route() == ROUTE_SRCOMMON, thr
         assert np.array_equal(g, O.common(files, thr)), thr
         gk, gt = ctx.common(files, thr, taxs)
-        assert ctx.last_route() == ROUTE_SR_COMMON, thr
+        assert ctx.last_route() == ROUTE_SRCOMMON, thr
         ok, ot = O.common(files, thr, taxs, tax)
         assert np.array_equal(gk, ok) and np.array_equal(gt, ot), thr
     # some files without taxids (read as 0), and the multi-level route gives the same
     taxs2 = [t if i % 4 else None for i, t in enumerate(taxs)]
     gk, gt = ctx.common(files, 120, taxs2)
-    assert ctx.last_route() == ROUTE_SR_COMMON
+    assert ctx.last_route() == ROUTE_SRCOMMON
     ok, ot = O.common(files, 120, taxs2, tax)
     assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
     monkeypatch.setenv("UKM_SRMERGE", "0")
     gk2, gt2 = ctx.common(files, 120, taxs2)
-    assert ctx.last_route() != ROUTE_SR_COMMON
+    assert ctx.last_route() != ROUTE_SRCOMMON
     assert np.array_equal(gk2, ok) and np.array_equal(gt2, ot)

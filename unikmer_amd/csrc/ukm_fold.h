@@ -1,7 +1,7 @@
 // ukm_fold.h — internal: `inter` / `diff` over many sorted streams as one range-partitioned launch (ukm_fold.hip)
 #pragma once
-#include "ukm_internal.h"
+#include "ukm_route.h"
 
 bool ukm_fold_enabled(const ukm_ctx *c);  // UKM_NO_FOLD=1 switches it off (developer knob)
-int ukm_dev_range_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax,
-                       u32 flags, u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback);
+// the route contract of ukm_route.h; op: UKM_OP_INTER / UKM_OP_DIFF
+int ukm_dev_range_fold(ukm_ctx *c, const UkmStreams &in, int op, u32 flags, const UkmOut &o, bool *declined);

@@ -27,6 +27,7 @@
 
 #include "ukm_device.h"
 #include "ukm_fold.h"
+#include "ukm_route.h"
 
 namespace {
 
@@ -465,52 +466,33 @@ void fd_fold_kernel(FoldArgs a) {
     if (wbad && lane_id() == 0) atomicOr((unsigned long long *)&a.ctl[1], (unsigned long long)wbad);
 }
 
-// ranges -> contiguous output: workgroup r copies its cnt[r] survivors to out[excl[r] ...)
-__global__ void fd_gather_kernel(const u64 *tmp_k, const u32 *tmp_t, const u64 *cnt, const u64 *excl, u64 *out, u32 *tout,
-                                 u64 out_cap, u32 range_len) {
-    const u32 r = blockIdx.x;
-    const u64 n = cnt[r], base = excl[r];
-    for (u64 i = threadIdx.x; i < n; i += blockDim.x) {
-        const u64 pos = base + i;
-        if (pos < out_cap) {
-            out[pos] = tmp_k[(size_t)r * range_len + i];
-            if (tout) tout[pos] = tmp_t ? tmp_t[(size_t)r * range_len + i] : 0u;
-        }
-    }
-}
-
 }  // namespace
 
 bool ukm_fold_enabled(const ukm_ctx *c) { return !ukm_env_is(c, "UKM_NO_FOLD", '1'); }
 
-// All pointers are device pointers; every stream is non-empty, sorted (the kernel verifies it) and the fold is the
-// reference's left fold of streams[1..] into streams[0].  *fallback: a duplicate code was seen (the caller takes the
-// exact multiset route); UKM_ERR_UNSORTED: an input is not sorted.
-int ukm_dev_range_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax,
-                       u32 flags, u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback) {
-    *fallback = false;
-    *n_out = 0;
+// Every stream is non-empty, sorted (the kernel verifies it) and the fold is the reference's left fold of streams[1..] into
+// streams[0].  Declines a shape it does not fit and a duplicate code (the caller takes the exact multiset route);
+// UKM_ERR_UNSORTED: an input is not sorted.
+int ukm_dev_range_fold(ukm_ctx *c, const UkmStreams &in, int op, u32 flags, const UkmOut &o, bool *declined) {
+    *declined = true;
+    *o.n = 0;
+    const int S = in.S;
+    const bool tax = in.tax;
+    const u64 *lens = in.lens;
     if (op != UKM_OP_INTER && op != UKM_OP_DIFF) UKM_FAIL(UKM_ERR_INVALID, "range fold: unknown op %d", op);
     if (S < 2 || lens[0] == 0) UKM_FAIL(UKM_ERR_INVALID, "range fold: needs two non-empty streams");
     const bool need_lca = tax && (op == UKM_OP_INTER || (flags & UKM_F_CMP_TAXID));
     if (need_lca && c->tax_parent == nullptr)
         UKM_FAIL(UKM_ERR_NO_TAXONOMY, "ukm_setop2: records carry taxids but no taxonomy is loaded");
-    if (tax && !tout) UKM_FAIL(UKM_ERR_INVALID, "range fold: taxids given but out_taxids is NULL");
+    if (tax && !o.taxids) UKM_FAIL(UKM_ERR_INVALID, "range fold: taxids given but out_taxids is NULL");
     // Range length: the whole fold is ONE round of resident workgroups when the first file allows it (a step costs a
     // latency, not a bandwidth: ~1000 dependent steps per workgroup, so a second round of workgroups doubles the time).
-    static std::atomic<int> slots_cache[4];  // (zero-initialised; racing first calls compute the same value)
-    const int vi = (op == UKM_OP_INTER ? 0 : 2) + (tax ? 1 : 0);
-    if (!slots_cache[vi].load(std::memory_order_relaxed)) {
-        int per_cu = 0;
-        hipError_t e;
-        if (vi == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fd_fold_kernel<UKM_OP_INTER, false>, FD_NT, 0);
-        else if (vi == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fd_fold_kernel<UKM_OP_INTER, true>, FD_NT, 0);
-        else if (vi == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fd_fold_kernel<UKM_OP_DIFF, false>, FD_NT, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fd_fold_kernel<UKM_OP_DIFF, true>, FD_NT, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 2;
-        slots_cache[vi].store(per_cu * c->num_cu, std::memory_order_relaxed);
-    }
-    const u64 slots = (u64)slots_cache[vi].load(std::memory_order_relaxed);
+    static std::atomic<int> slots_cache[4];
+    u64 slots;
+    if (op == UKM_OP_INTER) slots = tax ? ukm_resident_slots(c, slots_cache[1], fd_fold_kernel<UKM_OP_INTER, true>, FD_NT)
+                                        : ukm_resident_slots(c, slots_cache[0], fd_fold_kernel<UKM_OP_INTER, false>, FD_NT);
+    else slots = tax ? ukm_resident_slots(c, slots_cache[3], fd_fold_kernel<UKM_OP_DIFF, true>, FD_NT)
+                     : ukm_resident_slots(c, slots_cache[2], fd_fold_kernel<UKM_OP_DIFF, false>, FD_NT);
     u64 range_len = (lens[0] + slots - 1) / slots;
     range_len = std::max<u64>(range_len, FD_RANGE_MIN);
     range_len = std::min<u64>((range_len + FD_SPT - 1) / FD_SPT * FD_SPT, FD_RANGE_MAX);
@@ -526,18 +508,15 @@ int ukm_dev_range_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
         u64 rest = 0;
         for (int j = 1; j < S; j++) rest += lens[j];
         const u64 avg_slice = rest / (u64)(S - 1) / R64;
-        if (avg_slice > 4ull * FD_CH) {
-            *fallback = true;
-            return UKM_OK;
-        }
+        if (avg_slice > 4ull * FD_CH) return UKM_OK;
     }
 
-    // device tables: [meta S x 2][lens S]
+    // device tables: [meta S x 2][lens S] (the kernel loads a file's keys and taxids pointers, and its cuts, as pairs)
     const size_t ntab = (size_t)3 * S;
     std::vector<u64> tab(ntab);
     for (int j = 0; j < S; j++) {
-        tab[(size_t)2 * j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)2 * j + 1] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
+        tab[(size_t)2 * j] = (u64)(uintptr_t)in.keys[j];
+        tab[(size_t)2 * j + 1] = (u64)(uintptr_t)((tax && in.taxids) ? in.taxids[j] : nullptr);
         tab[(size_t)2 * S + j] = lens[j];
     }
     u64 *d_tab = nullptr;
@@ -554,12 +533,10 @@ int ukm_dev_range_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
     a.range_len = (u32)range_len;
     a.T = ukm_taxdev(c);
     a.flags = flags;
-    u64 *excl = nullptr;
     UKM_TRY(ws_alloc_t(c, (size_t)R * S * 2, &a.cuts));
     UKM_TRY(ws_alloc_t(c, (size_t)R * range_len, &a.tmp_k));
     if (tax) UKM_TRY(ws_alloc_t(c, (size_t)R * range_len, &a.tmp_t));
     UKM_TRY(ws_alloc_t(c, (size_t)R, &a.cnt));
-    UKM_TRY(ws_alloc_t(c, (size_t)R + 1, &excl));
     UKM_TRY(ws_alloc_t(c, 8, &a.ctl));
     UKM_HIP(hipMemsetAsync(a.ctl, 0, 8 * sizeof(u64), c->stream));
 
@@ -576,23 +553,18 @@ int ukm_dev_range_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
     (void)hipEventRecord(c->ev_k1, c->stream);
     c->evk_valid = true;
     UKM_HIP(hipGetLastError());
-    UKM_TRY(ukm_dev_exclusive_scan_u64(c, a.cnt, excl, R, a.ctl));  // ctl[0] = total
-    hipLaunchKernelGGL(fd_gather_kernel, dim3(R), dim3(256), 0, c->stream, a.tmp_k, tax ? a.tmp_t : nullptr, a.cnt, excl, out,
-                       tax ? tout : nullptr, out_cap, a.range_len);
-    UKM_HIP(hipGetLastError());
-    u64 h[2] = {0, 0};
-    UKM_TRY(ukm_read_u64(c, a.ctl, h, 2));
+    RangeGather g;
+    g.src_k = a.tmp_k;
+    g.src_t = a.tmp_t;
+    g.stride = range_len;
+    g.cnt = a.cnt;
+    g.R = R;
+    u64 h[2];
+    UKM_TRY(ukm_range_finish(c, g, a.ctl, o, h));
     if (ukm_env(c, "UKM_FOLD_DEBUG"))
         fprintf(stderr, "[fold] op=%d S=%d R=%u range_len=%llu slots=%llu tax=%d flags=%llu out=%llu\n", op, S, R,
                 (unsigned long long)range_len, (unsigned long long)slots, (int)tax, (unsigned long long)h[1], (unsigned long long)h[0]);
     if (h[1] & FD_FLAG_UNSORTED) UKM_FAIL(UKM_ERR_UNSORTED, "ukm_setop2: an input stream is not sorted");
-    if (h[1] & FD_FLAG_DUP) {
-        *fallback = true;
-        return UKM_OK;
-    }
-    *n_out = h[0];
-    if (h[0] > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu records, capacity is %llu", (unsigned long long)h[0],
-                 (unsigned long long)out_cap);
-    return UKM_OK;
+    if (h[1] & FD_FLAG_DUP) return UKM_OK;
+    return ukm_route_answer(h[0], o, declined);
 }

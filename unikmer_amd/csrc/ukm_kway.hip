@@ -568,20 +568,6 @@ __global__ void kw_prefix_kernel(const u64 *cuts, u32 S, u32 R, u64 *P) {
     P[(u64)S * RP + r] = acc;
 }
 
-// gather the ranges of the last union level into the caller's buffer: range r goes to dst + excl[r]
-__global__ void kw_compact_kernel(const u64 *src, const u32 *tsrc, const u64 *P, u32 S, u32 R, const u64 *cnt,
-                                  const u64 *excl, u64 *dst, u32 *tdst, u64 cap, int parts) {
-    const u32 r = blockIdx.x / parts, part = blockIdx.x % parts;
-    const u64 RP = (u64)R + 1;
-    const u64 off = P[(u64)S * RP + r];
-    const u64 n = cnt[r], d0 = excl[r];
-    if (d0 + n > cap) return;  // the host reports UKM_ERR_CAPACITY
-    const u64 lo = n * part / parts, hi = n * (part + 1) / parts;
-    for (u64 i = lo + threadIdx.x; i < hi; i += blockDim.x) dst[d0 + i] = src[off + i];
-    if (tsrc)
-        for (u64 i = lo + threadIdx.x; i < hi; i += blockDim.x) tdst[d0 + i] = tsrc[off + i];
-}
-
 // Shapes.  ONE LDS buffer, 256 threads, VT = 9 records per thread for K = 4 and 8 (19 KB plain / 28 KB with TaxIds);
 // K = 16 (UKM_KWAY_K=16, plain keys only): 512 threads, VT = 17, 70 KB.  VT is odd so that the threads' consecutive
 // 8-byte LDS accesses fall into different banks, and VT = M * K + 1 gives the division-free chunk layout.
@@ -630,14 +616,19 @@ static bool kw_top2_enabled(const ukm_ctx *c) { return !ukm_env_is(c, "UKM_KWAY_
 
 bool ukm_kway_enabled(const ukm_ctx *c) { return !ukm_env_is(c, "UKM_NO_KWAY", '1'); }
 
-// All pointers are device pointers.  op: UKM_KWAY_UNION / UKM_KWAY_MERGE.  *fallback is set when the inputs
-// need the caller's general route (unsorted stream, degenerate run); the output is then undefined.
-int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S,
-                 bool tax, u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback) {
-    *fallback = false;
-    *n_out = 0;
+// The route contract of ukm_route.h.  op: UKM_KWAY_UNION / UKM_KWAY_MERGE.  Declines an unsorted stream and a
+// degenerate run (the caller's general route answers).
+int ukm_dev_kway(ukm_ctx *c, const UkmStreams &in, int op, const UkmOut &o, bool *declined) {
+    *declined = true;
+    *o.n = 0;
+    const int S = in.S;
+    const bool tax = in.tax;
+    const u64 *lens = in.lens;
+    u64 *const out = o.keys;
+    u32 *const tout = o.taxids;
+    const u64 out_cap = o.cap;
     const bool uni = op == UKM_KWAY_UNION;
-    if (S <= 0) return UKM_OK;
+    if (S <= 0) return ukm_route_answer(0, o, declined);
     if (tax && !tout) UKM_FAIL(UKM_ERR_INVALID, "k-way merge: taxids given but out_taxids is NULL");
     if (tax && uni && c->tax_parent == nullptr)
         UKM_FAIL(UKM_ERR_NO_TAXONOMY, "k-way union: records carry taxids but no taxonomy is loaded");
@@ -646,9 +637,9 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
         N += lens[j];
         nmax = std::max<u64>(nmax, lens[j]);
     }
-    if (N == 0) return UKM_OK;
+    if (N == 0) return ukm_route_answer(0, o, declined);
     if (!uni && N > out_cap) {
-        *n_out = N;
+        *o.n = N;
         UKM_FAIL(UKM_ERR_CAPACITY, "k-way merge: output needs %llu records, capacity is %llu", (unsigned long long)N,
                  (unsigned long long)out_cap);
     }
@@ -664,15 +655,8 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
     int K = pick_k((u64)S);
     // UKM_KWAY_DEBUG=1: per-phase device times on stderr (developer knob; adds events + one sync)
     const bool dbg = ukm_env(c, "UKM_KWAY_DEBUG") != nullptr;
-    std::vector<std::pair<const char *, hipEvent_t>> marks;
-    auto mark = [&](const char *name) {
-        if (!dbg) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) == hipSuccess) {
-            (void)hipEventRecord(e, c->stream);
-            marks.emplace_back(name, e);
-        }
-    };
+    PhaseMarks marks(dbg, c->stream);
+    auto mark = [&](const char *name) { marks.mark(name); };
     mark("start");
     int levels = 0;
     for (u64 nn = (u64)S; ; ) { const int kk = pick_k(nn); levels++; nn = (nn + kk - 1) / kk; if (nn <= 1) break; }
@@ -712,24 +696,13 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
     const u32 R = (u32)R64;
     const u64 RP = (u64)R + 1;
 
-    // ---- device tables ---------------------------------------------------------------------------------------
-    // [leaf_keys S][leaf_tax S][leaf_len S][sample_base S+1]
-    const size_t ntab = (size_t)4 * S + 1;
-    std::vector<u64> tab(ntab);
-    for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
-        tab[(size_t)2 * S + j] = lens[j];
-    }
-    for (int j = 0; j <= S; j++) tab[(size_t)3 * S + j] = sample_base[(size_t)j];
-    u64 *d_tab = nullptr;
-    UKM_TRY(ws_alloc_t(c, ntab, &d_tab));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), ntab * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
-    const u64 *const *d_keys = reinterpret_cast<const u64 *const *>(d_tab);
-    const u32 *const *d_tax = reinterpret_cast<const u32 *const *>(d_tab + S);
-    const u64 *d_len = d_tab + 2 * (size_t)S;
-    const u64 *d_sbase = d_tab + 3 * (size_t)S;
+    // ---- device tables: the streams, then sample_base S + 1 -------------------------------------------------------
+    StreamTab tab;
+    UKM_TRY(ukm_stream_tab(c, in, &tab, sample_base.data(), sample_base.size()));
+    const u64 *const *d_keys = tab.keys();
+    const u32 *const *d_tax = tab.taxids();
+    const u64 *d_len = tab.lens();
+    const u64 *d_sbase = tab.extra();
 
     u64 *cuts = nullptr, *P = nullptr, *ctl = nullptr;
     UKM_TRY(ws_alloc_t(c, (size_t)S * RP, &cuts));
@@ -786,8 +759,6 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
             u64 fl = 0;
             UKM_TRY(ukm_read_u64(c, ctl + 1, &fl));
             if (fl & (KW_FLAG_UNSORTED | KW_FLAG_DEGENERATE)) {
-                if (dbg) for (auto &m : marks) (void)hipEventDestroy(m.second);
-                *fallback = true;
                 return UKM_OK;
             }
             u64 nA = 0;
@@ -837,8 +808,6 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
             u64 fl = 0;
             UKM_TRY(ukm_read_u64(c, ctl + 1, &fl));
             if (fl & (KW_FLAG_UNSORTED | KW_FLAG_DEGENERATE)) {
-                if (dbg) for (auto &m : marks) (void)hipEventDestroy(m.second);
-                *fallback = true;
                 return UKM_OK;
             }
         }
@@ -851,37 +820,25 @@ int ukm_dev_kway(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *t
         nprev = nodes;
         span *= (u64)K;
     }
-    u64 h[2] = {0, 0};
+    // (a union: ranges of the root -> contiguous output)
+    RangeGather g;
     if (uni) {
-        // ranges of the root -> contiguous output
-        u64 *excl = nullptr;
-        UKM_TRY(ws_alloc_t(c, (size_t)R + 1, &excl));
-        UKM_TRY(ukm_dev_exclusive_scan_u64(c, last_cnt, excl, R, ctl));  // ctl[0] = total
-        const int parts = R >= 2048 ? 1 : (int)std::min<u64>(64, std::max<u64>(1, 2048 / R));
-        hipLaunchKernelGGL(kw_compact_kernel, dim3(R * (unsigned)parts), dim3(256), 0, c->stream, last_k, tax ? last_t : nullptr,
-                           P, (u32)S, R, last_cnt, excl, out, tout, out_cap, parts);
-        UKM_HIP(hipGetLastError());
+        g.src_k = last_k;
+        g.src_t = tax ? last_t : nullptr;
+        g.slot = P + (size_t)S * RP;
+        g.cnt = last_cnt;
+        g.R = R;
+        g.parts = R >= 2048 ? 1 : (int)std::min<u64>(64, std::max<u64>(1, 2048 / R));
     }
+    u64 h[2];
+    UKM_TRY(ukm_range_finish(c, g, ctl, o, h));
     mark("compact");
-    UKM_TRY(ukm_read_u64(c, ctl, h, 2));
     if (dbg) {
         fprintf(stderr, "[kway] S=%d N=%llu K=%d levels=%d R=%u ns=%llu flags=%llu out=%llu :", S, (unsigned long long)N, K,
                 levels, R, (unsigned long long)ns, (unsigned long long)h[1], (unsigned long long)h[0]);
-        for (size_t i = 1; i < marks.size(); i++) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, marks[i - 1].second, marks[i].second);
-            fprintf(stderr, " %s=%.3fms", marks[i].first, ms);
-        }
+        marks.print();
         fprintf(stderr, "\n");
-        for (auto &m : marks) (void)hipEventDestroy(m.second);
     }
-    if (h[1] & (KW_FLAG_UNSORTED | KW_FLAG_DEGENERATE)) {
-        *fallback = true;
-        return UKM_OK;
-    }
-    *n_out = uni ? h[0] : N;
-    if (*n_out > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "k-way union: output needs %llu records, capacity is %llu", (unsigned long long)*n_out,
-                 (unsigned long long)out_cap);
-    return UKM_OK;
+    if (h[1] & (KW_FLAG_UNSORTED | KW_FLAG_DEGENERATE)) return UKM_OK;
+    return ukm_route_answer(uni ? h[0] : N, o, declined);
 }

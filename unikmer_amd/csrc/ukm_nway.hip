@@ -173,6 +173,39 @@ struct OutBufs {
     u32 *t = nullptr;
 };
 
+// The non-empty streams as the device routes take them (ukm_route.h).
+struct RouteStreams {
+    std::vector<const u64 *> k;
+    std::vector<const u32 *> t;
+    std::vector<u64> n;
+    std::vector<u32> ct;  // the file taxid of a stream without per-record taxids
+    explicit RouteStreams(const std::vector<Stream> &ss) {
+        for (auto &q : ss)
+            if (q.n) {
+                k.push_back(q.k);
+                t.push_back(q.t);
+                n.push_back(q.n);
+                ct.push_back(q.t ? 0u : q.ct);
+            }
+    }
+    int size() const { return (int)k.size(); }
+    UkmStreams view(bool tax) const { return UkmStreams{k.data(), tax ? t.data() : nullptr, tax ? ct.data() : nullptr, n.data(), size(), tax}; }
+};
+
+// One attempt at a device route, under the contract of ukm_route.h: the workspace it used is given back, and when it
+// answers *done is set and `route` recorded (UKM_ROUTE_NONE for the folds of inter / diff, which have no id of their own).
+template <typename F>
+int attempt(ukm_ctx *ctx, int route, bool *done, F call) {
+    WsMark mark = ws_mark(ctx);
+    bool declined = true;
+    const int rc = call(&declined);
+    ws_release(ctx, mark);
+    UKM_TRY(rc);
+    *done = !declined;
+    if (*done) ctx->last_route = route;
+    return UKM_OK;
+}
+
 template <typename F>
 int run_entry(ukm_ctx *ctx, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out,
               bool tax, F body) {
@@ -184,7 +217,7 @@ int run_entry(ukm_ctx *ctx, uint64_t *out_keys, uint32_t *out_taxids, uint64_t o
         if (tax && !out_taxids) UKM_FAIL(UKM_ERR_INVALID, "records carry taxids but out_taxids is NULL");
         if (tax) UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &o.t));
         *n_out = 0;
-        ctx->last_route = 0;
+        ctx->last_route = UKM_ROUTE_NONE;
         int r = body(o);
         u64 n = (r == UKM_OK) ? *n_out : 0;
         ukm_out_resize(ctx, out_keys, n * sizeof(u64));
@@ -205,7 +238,7 @@ int tree_reduce(ukm_ctx *ctx, std::vector<Stream> ss, int op, u32 flags, bool ta
                 bool lazy_normalise = false) {
     u64 total = 0;
     for (auto &s : ss) total += s.n;
-    ctx->last_route = ss.size() > 2 ? 1 : 0;
+    ctx->last_route = ss.size() > 2 ? UKM_ROUTE_TREE : UKM_ROUTE_NONE;
     std::vector<char> orig(ss.size(), lazy_normalise ? 1 : 0);
     u64 *bk[2] = {nullptr, nullptr};
     u32 *bt[2] = {nullptr, nullptr};
@@ -276,59 +309,22 @@ int try_kway(ukm_ctx *ctx, int op, std::vector<Stream> ss, bool tax, u64 *fk, u3
         const bool forced = ukm_env_is(ctx, "UKM_KWAY", '1');
         if (!forced && ss.size() <= 4 && total < (1u << 16)) return UKM_OK;
     }
-    std::vector<const u64 *> kp(ss.size());
-    std::vector<const u32 *> tp(ss.size());
-    std::vector<u64> ln(ss.size());
-    std::vector<u32> cv(ss.size());
-    for (size_t i = 0; i < ss.size(); i++) {
-        kp[i] = ss[i].k;
-        tp[i] = ss[i].t;
-        ln[i] = ss[i].n;
-        cv[i] = ss[i].t ? 0u : ss[i].ct;
-    }
-    bool fallback = true;
+    const UkmOut o{fk, ft, fcap, n_out};
     if (op == UKM_KWAY_MERGE) {
         // many files that share most of their codes: the records of every code are placed behind one another file by file
         // (ukm_punion.hip, pl_merge_kernel); it declines for few / small files, files that share little, a duplicate
         // inside a file, an unsorted file.  (A file with ONE taxid goes in as it is: the kernel writes the scalar.)
-        WsMark pmark = ws_mark(ctx);
-        const int prc = ukm_dev_place_merge(ctx, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, fk, ft, fcap, n_out,
-                                            &fallback, tax ? cv.data() : nullptr);
-        if (prc != UKM_OK || !fallback) {
-            ws_release(ctx, pmark);
-            UKM_TRY(prc);
-            ctx->last_route = 7;
-            *done = true;
-            return UKM_OK;
-        }
-        ws_release(ctx, pmark);
-        fallback = true;
+        const RouteStreams rs(ss);
+        UKM_TRY(attempt(ctx, UKM_ROUTE_PLACE, done, [&](bool *d) { return ukm_dev_place_merge(ctx, rs.view(tax), o, d); }));
+        if (*done) return UKM_OK;
     }
     UKM_TRY(materialise_all(ctx, ss, tax));  // (the merges below read a taxid per record)
-    for (size_t i = 0; i < ss.size(); i++) tp[i] = ss[i].t;
-    WsMark mark = ws_mark(ctx);
-    {
-        // many short streams: one pass over HBM, every value range ordered inside LDS (ukm_srmerge.hip); it declines
-        // (*fallback) for few streams, small inputs, unsorted streams and one code with thousands of copies
-        const int src = ukm_dev_srmerge(ctx, op, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, fk, ft, fcap,
-                                        n_out, &fallback);
-        if (src != UKM_OK || !fallback) {
-            ws_release(ctx, mark);
-            UKM_TRY(src);
-            ctx->last_route = 4;
-            *done = true;
-            return UKM_OK;
-        }
-        ws_release(ctx, mark);
-    }
-    fallback = false;
-    const int rc = ukm_dev_kway(ctx, op, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, fk, ft, fcap,
-                                n_out, &fallback);
-    ws_release(ctx, mark);
-    UKM_TRY(rc);
-    *done = !fallback;
-    if (*done) ctx->last_route = 2;
-    return UKM_OK;
+    const RouteStreams rs(ss);
+    // many short streams: one pass over HBM, every value range ordered inside LDS (ukm_srmerge.hip); it declines for few
+    // streams, small inputs, unsorted streams and one code with thousands of copies
+    UKM_TRY(attempt(ctx, UKM_ROUTE_SRMERGE, done, [&](bool *d) { return ukm_dev_srmerge(ctx, rs.view(tax), op, 0, o, d); }));
+    if (*done) return UKM_OK;
+    return attempt(ctx, UKM_ROUTE_KWAY, done, [&](bool *d) { return ukm_dev_kway(ctx, rs.view(tax), op, o, d); });
 }
 
 // `union` of many sets by LDS hash probes against the union of the first eight (with TaxIds: four) files
@@ -350,25 +346,9 @@ int try_probe_union(ukm_ctx *ctx, const std::vector<Stream> &ss, bool tax, u64 *
         //  3.3 - 4.8 ms; 3e7 records 1.4 - 3.5 against 1.3 - 2.8)
         if (later < (tax ? (1ull << 26) : (1ull << 27))) return UKM_OK;
     }
-    std::vector<const u64 *> kp(ss.size());
-    std::vector<const u32 *> tp(ss.size());
-    std::vector<u64> ln(ss.size());
-    std::vector<u32> cv(ss.size());
-    for (size_t i = 0; i < ss.size(); i++) {
-        kp[i] = ss[i].k;
-        tp[i] = ss[i].t;
-        ln[i] = ss[i].n;
-        cv[i] = ss[i].t ? 0u : ss[i].ct;
-    }
-    WsMark mark = ws_mark(ctx);
-    bool fallback = false;
-    const int rc = ukm_dev_probe_union(ctx, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, fk, ft, fcap, n_out,
-                                       &fallback, tax ? cv.data() : nullptr);
-    ws_release(ctx, mark);
-    UKM_TRY(rc);
-    *done = !fallback;
-    if (*done) ctx->last_route = 3;
-    return UKM_OK;
+    const RouteStreams rs(ss);
+    return attempt(ctx, UKM_ROUTE_PUNION, done,
+                   [&](bool *d) { return ukm_dev_probe_union(ctx, rs.view(tax), false, UkmOut{fk, ft, fcap, n_out}, d); });
 }
 
 // All records of the (non-empty) streams as ONE sequence ordered by code, equal codes in stream
@@ -501,35 +481,14 @@ int try_range_fold(ukm_ctx *ctx, int op, std::vector<Stream> ss, u32 flags, bool
     *done = false;
     if (!ukm_fold_enabled(ctx) || ss.size() < (size_t)CHAIN_MIN_STREAMS || ss[0].n == 0 || ss[0].n > FOLD_MAX_FIRST) return UKM_OK;
     UKM_TRY(materialise_all(ctx, ss, tax));  // (files with one taxid each beside files with one per record: rare; all per file: the callers' fills)
-    std::vector<const u64 *> kp(ss.size());
-    std::vector<const u32 *> tp(ss.size());
-    std::vector<u64> ln(ss.size());
-    for (size_t i = 0; i < ss.size(); i++) {
-        kp[i] = ss[i].k;
-        tp[i] = ss[i].t;
-        ln[i] = ss[i].n;
-    }
+    const RouteStreams rs(ss);
+    const UkmOut o{fk, ft, fcap, n_out};
     if (ukm_pfold_enabled(ctx)) {
         // the order-independent rules (inter without --mix-taxid, diff without -t) by hash probes (ukm_pfold.hip)
-        WsMark pm = ws_mark(ctx);
-        bool fb = true;
-        const int prc = ukm_dev_probe_fold(ctx, op, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, flags, fk, ft,
-                                           fcap, n_out, &fb);
-        ws_release(ctx, pm);
-        UKM_TRY(prc);
-        if (!fb) {
-            *done = true;
-            return UKM_OK;
-        }
+        UKM_TRY(attempt(ctx, UKM_ROUTE_NONE, done, [&](bool *d) { return ukm_dev_probe_fold(ctx, rs.view(tax), op, flags, o, d); }));
+        if (*done) return UKM_OK;
     }
-    WsMark mark = ws_mark(ctx);
-    bool fallback = false;
-    const int rc = ukm_dev_range_fold(ctx, op, kp.data(), tax ? tp.data() : nullptr, ln.data(), (int)ss.size(), tax, flags, fk, ft,
-                                      fcap, n_out, &fallback);
-    ws_release(ctx, mark);
-    UKM_TRY(rc);
-    *done = !fallback;
-    return UKM_OK;
+    return attempt(ctx, UKM_ROUTE_NONE, done, [&](bool *d) { return ukm_dev_range_fold(ctx, rs.view(tax), op, flags, o, d); });
 }
 
 }  // namespace
@@ -821,22 +780,6 @@ static bool common_probe_enabled(const ukm_ctx *c) { return !ukm_env_is(c, "UKM_
 
 namespace {
 
-struct StreamTables {
-    std::vector<const u64 *> kp;
-    std::vector<const u32 *> tp;
-    std::vector<u64> ln;
-    std::vector<u32> cv;  // the file taxid of a stream without per-record taxids
-    explicit StreamTables(const std::vector<Stream> &ss, bool skip_empty) {
-        for (auto &q : ss)
-            if (q.n || !skip_empty) {
-                kp.push_back(q.k);
-                tp.push_back(q.t);
-                ln.push_back(q.n);
-                cv.push_back(q.t ? 0u : q.ct);
-            }
-    }
-};
-
 // common.go:220-344 over staged streams
 int common_body(ukm_ctx *ctx, std::vector<Stream> &ss, u32 threshold, bool tax, OutBufs &o, u64 out_cap, u64 *n_out, bool *probe_fold_done) {
     const int nstreams = (int)ss.size();
@@ -850,18 +793,15 @@ int common_body(ukm_ctx *ctx, std::vector<Stream> &ss, u32 threshold, bool tax, 
         bool eligible = ss[0].n <= FOLD_MAX_FIRST;
         for (auto &q : ss) eligible = eligible && q.n > 0 && (!tax || q.t != nullptr);
         if (eligible) {
-            StreamTables st(ss, false);
-            WsMark pm = ws_mark(ctx);
-            bool fb = true;
-            const int prc = ukm_dev_probe_fold(ctx, UKM_OP_INTER, st.kp.data(), tax ? st.tp.data() : nullptr, st.ln.data(), nstreams, tax, 0,
-                                               o.k, o.t, out_cap, n_out, &fb);
-            ws_release(ctx, pm);
-            UKM_TRY(prc);
-            if (!fb) {
+            const RouteStreams rs(ss);
+            bool done = false;
+            UKM_TRY(attempt(ctx, UKM_ROUTE_NONE, &done, [&](bool *d) {
+                return ukm_dev_probe_fold(ctx, rs.view(tax), UKM_OP_INTER, 0, UkmOut{o.k, o.t, out_cap, n_out}, d);
+            }));
+            if (done) {
                 if (probe_fold_done) *probe_fold_done = true;
                 return UKM_OK;
             }
-            *n_out = 0;
         }
     }
     if (probe_fold_done) return UKM_OK;  // (the caller only wanted the fold over plain codes)
@@ -892,18 +832,12 @@ int common_body(ukm_ctx *ctx, std::vector<Stream> &ss, u32 threshold, bool tax, 
         // first file's codes (and claim what the later files add), a record count and the TaxId fold per entry
         // (ukm_punion.hip, pt_probe_kernel<true>).  It declines for few / small files, later files that share too
         // little with the first, an unsorted file.
-        StreamTables st(ss, true);
-        WsMark pm = ws_mark(ctx);
-        bool fb = true;
-        const int prc = ukm_dev_probe_common(ctx, st.kp.data(), tax ? st.tp.data() : nullptr, st.ln.data(), (int)st.kp.size(), tax, threshold, o.k,
-                                             o.t, out_cap, n_out, &fb, true, tax ? st.cv.data() : nullptr);
-        ws_release(ctx, pm);
-        UKM_TRY(prc);
-        if (!fb) {
-            ctx->last_route = 6;
-            return UKM_OK;
-        }
-        *n_out = 0;
+        const RouteStreams rs(ss);
+        bool done = false;
+        UKM_TRY(attempt(ctx, UKM_ROUTE_PCOMMON, &done, [&](bool *d) {
+            return ukm_dev_probe_common(ctx, rs.view(tax), threshold, true, UkmOut{o.k, o.t, out_cap, n_out}, d);
+        }));
+        if (done) return UKM_OK;
     }
     UKM_TRY(materialise_all(ctx, ss, tax));  // (the merges below read a taxid per record)
     if (threshold > 1 && ukm_kway_enabled(ctx)) {
@@ -911,19 +845,13 @@ int common_body(ukm_ctx *ctx, std::vector<Stream> &ss, u32 threshold, bool tax, 
         // its tiles and writes only the codes that reach the threshold (ukm_srmerge.hip) -- otherwise the whole
         // merged sequence is written and read once more by the counting scan below.  It declines for few files,
         // small inputs, an unsorted file and a code with thousands of copies.
-        StreamTables st(ss, true);
-        if (st.kp.size() >= 3) {
-            WsMark pm = ws_mark(ctx);
-            bool fb = true;
-            const int src = ukm_dev_srmerge(ctx, UKM_KWAY_UNION, st.kp.data(), tax ? st.tp.data() : nullptr, st.ln.data(), (int)st.kp.size(), tax,
-                                            o.k, o.t, out_cap, n_out, &fb, threshold);
-            ws_release(ctx, pm);
-            UKM_TRY(src);
-            if (!fb) {
-                ctx->last_route = 5;
-                return UKM_OK;
-            }
-            *n_out = 0;
+        const RouteStreams rs(ss);
+        if (rs.size() >= 3) {
+            bool done = false;
+            UKM_TRY(attempt(ctx, UKM_ROUTE_SRCOMMON, &done, [&](bool *d) {
+                return ukm_dev_srmerge(ctx, rs.view(tax), UKM_KWAY_UNION, threshold, UkmOut{o.k, o.t, out_cap, n_out}, d);
+            }));
+            if (done) return UKM_OK;
         }
     }
     u64 *k = nullptr;
@@ -1001,19 +929,13 @@ extern "C" int ukm_merge_k_ft(ukm_ctx *ctx, const uint64_t *const *keys, const u
             // (util-sort.go:519-530): for many files that share most of their codes the counting hash probes of
             // ukm_punion.hip with a threshold of two (every record of every file counts); it declines for few / small /
             // unsorted files and files that share little, and the merge + scan below answers.
-            StreamTables st(all, true);
-            if (st.kp.size() >= 3) {
-                WsMark pm = ws_mark(ctx);
-                bool fb = true;
-                const int prc = ukm_dev_probe_common(ctx, st.kp.data(), tax ? st.tp.data() : nullptr, st.ln.data(), (int)st.kp.size(), tax, 2u, o.k, o.t,
-                                                     out_cap, n_out, &fb, false, tax ? st.cv.data() : nullptr);
-                ws_release(ctx, pm);
-                UKM_TRY(prc);
-                if (!fb) {
-                    ctx->last_route = 6;
-                    return UKM_OK;
-                }
-                *n_out = 0;
+            const RouteStreams rs(all);
+            if (rs.size() >= 3) {
+                bool done = false;
+                UKM_TRY(attempt(ctx, UKM_ROUTE_PCOMMON, &done, [&](bool *d) {
+                    return ukm_dev_probe_common(ctx, rs.view(tax), 2u, false, UkmOut{o.k, o.t, out_cap, n_out}, d);
+                }));
+                if (done) return UKM_OK;
             }
         }
         {

@@ -26,6 +26,7 @@
 
 #include "ukm_device.h"
 #include "ukm_pfold.h"
+#include "ukm_route.h"
 
 namespace {
 
@@ -46,8 +47,8 @@ constexpr u64 PF_EMPTY = ~0ull;
 enum { PF_FLAG_DUP = 1, PF_FLAG_UNSORTED = 2 };
 
 struct PfArgs {
-    const u64 *tab;  // [keys S][taxids S][lens S] (device copies of the caller's tables)
-    u32 S, R, L;
+    StreamTab tab;   // the streams (ukm_route.h)
+    u32 R, L;
     u64 *cuts;       // [R + 1][S - 1]: lower bound of file0[r * L] in file j (j = 1 .. S - 1)
     u64 *tmp_k;      // [R][L]
     u32 *tmp_t;
@@ -59,32 +60,6 @@ struct PfArgs {
 __device__ __forceinline__ u32 pf_hash(u64 x) {
     const u32 lo = (u32)x, hi = (u32)(x >> 32);
     return ((lo ^ __builtin_rotateleft32(hi, 15) ^ (hi >> 3)) * 0x9E3779B1u) >> (32 - PF_BUCKET_BITS);
-}
-
-__global__ void pf_cuts_kernel(PfArgs a) {
-    const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 per = (u64)a.R + 1;
-    const u32 S1 = a.S - 1;
-    if (gid >= per * S1) return;
-    const u32 j = (u32)(gid / per) + 1, r = (u32)(gid % per);
-    const u64 len = a.tab[2 * (u64)a.S + j];
-    u64 res;
-    if (r == 0) {
-        res = 0;
-    } else if (r == a.R) {
-        res = len;
-    } else {
-        const auto f0 = as_global((const u64 *)(uintptr_t)a.tab[0]);
-        const auto f = as_global((const u64 *)(uintptr_t)a.tab[j]);
-        const u64 v = f0[(u64)r * a.L];
-        u64 lo = 0, hi = len;
-        while (lo < hi) {
-            const u64 mid = (lo + hi) >> 1;
-            if (f[mid] < v) lo = mid + 1; else hi = mid;
-        }
-        res = lo;
-    }
-    a.cuts[(u64)r * S1 + (j - 1)] = res;
 }
 
 typedef u64 pf_u64x2 __attribute__((ext_vector_type(2)));
@@ -113,10 +88,10 @@ void pf_probe_kernel(PfArgs a) {
     __shared__ u32 s_next, s_done, s_dead;  // s_dead: no record of the range can survive any more
     constexpr bool FOLD_TAX = TAX && (OP == UKM_OP_INTER || CMP);  // the later files' taxids are read
     const int tid = (int)threadIdx.x, lane = lane_id();
-    const u32 r = blockIdx.x, S = a.S, S1 = S - 1, L = a.L;
-    const auto f0 = as_global((const u64 *)(uintptr_t)sload_u64(&a.tab[0]));
-    const auto t0 = as_global((const u32 *)(uintptr_t)sload_u64(&a.tab[S]));
-    const u64 len0 = sload_u64(&a.tab[2 * (u64)S]);
+    const u32 r = blockIdx.x, S = a.tab.S, S1 = S - 1, L = a.L;
+    const auto f0 = as_global((const u64 *)(uintptr_t)sload_u64(&a.tab.d[0]));
+    const auto t0 = as_global((const u32 *)(uintptr_t)sload_u64(&a.tab.d[S]));
+    const u64 len0 = sload_u64(&a.tab.d[2 * (u64)S]);
     const u64 e0 = (u64)r * L;
     const u32 ne = (u32)((len0 - e0 < (u64)L) ? (len0 - e0) : (u64)L);
     for (int i = tid; i < PF_SLOTS; i += NT) s_tab[i] = PF_EMPTY;
@@ -383,9 +358,9 @@ void pf_probe_kernel(PfArgs a) {
         if (j < S1) {
             m.beg = sload_u64(&a.cuts[(u64)r * S1 + j]);
             m.end = sload_u64(&a.cuts[(u64)(r + 1) * S1 + j]);
-            m.f = sload_u64(&a.tab[j + 1]);
-            m.t = sload_u64(&a.tab[(u64)S + j + 1]);
-            m.len = sload_u64(&a.tab[2 * (u64)S + j + 1]);
+            m.f = sload_u64(&a.tab.d[j + 1]);
+            m.t = sload_u64(&a.tab.d[(u64)S + j + 1]);
+            m.len = sload_u64(&a.tab.d[2 * (u64)S + j + 1]);
         }
         return m;
     };
@@ -476,28 +451,16 @@ void pf_probe_kernel(PfArgs a) {
     if (tid == 0) a.cnt[r] = base;
 }
 
-// ranges -> contiguous output: workgroup r copies its cnt[r] survivors to out[excl[r] ...)
-__global__ void pf_gather_kernel(const u64 *tmp_k, const u32 *tmp_t, const u64 *cnt, const u64 *excl, u64 *out, u32 *tout,
-                                 u64 out_cap, u32 L) {
-    const u32 r = blockIdx.x;
-    const u64 n = cnt[r], base = excl[r];
-    for (u64 i = threadIdx.x; i < n; i += blockDim.x) {
-        const u64 pos = base + i;
-        if (pos < out_cap) {
-            out[pos] = tmp_k[(size_t)r * L + i];
-            if (tout) tout[pos] = tmp_t ? tmp_t[(size_t)r * L + i] : 0u;
-        }
-    }
-}
-
 }  // namespace
 
 bool ukm_pfold_enabled(const ukm_ctx *c) { return !ukm_env_is(c, "UKM_NO_PFOLD", '1'); }
 
-int ukm_dev_probe_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax,
-                       u32 flags, u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback) {
-    *fallback = true;
-    *n_out = 0;
+int ukm_dev_probe_fold(ukm_ctx *c, const UkmStreams &in, int op, u32 flags, const UkmOut &o, bool *declined) {
+    *declined = true;
+    *o.n = 0;
+    const int S = in.S;
+    const bool tax = in.tax;
+    const u64 *lens = in.lens;
     if (op != UKM_OP_INTER && op != UKM_OP_DIFF) return UKM_OK;
     if (op == UKM_OP_INTER && (flags & UKM_F_MIX_TAXID)) return UKM_OK;
     const bool cmp = op == UKM_OP_DIFF && tax && (flags & UKM_F_CMP_TAXID);
@@ -510,18 +473,12 @@ int ukm_dev_probe_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
         if (lens[j] == 0) return UKM_OK;  // (the caller drops / truncates at empty files; anything else: not here)
     if (tax && (op == UKM_OP_INTER || cmp) && c->tax_parent == nullptr)
         UKM_FAIL(UKM_ERR_NO_TAXONOMY, "ukm_setop2: records carry taxids but no taxonomy is loaded");
-    if (tax && !tout) UKM_FAIL(UKM_ERR_INVALID, "probe fold: taxids given but out_taxids is NULL");
+    if (tax && !o.taxids) UKM_FAIL(UKM_ERR_INVALID, "probe fold: taxids given but out_taxids is NULL");
     // one round of resident workgroups when the first file allows it
     const bool euler = op == UKM_OP_INTER && tax;
     static std::atomic<int> slots_cache[2];
-    if (!slots_cache[euler].load(std::memory_order_relaxed)) {
-        int per_cu = 0;
-        const hipError_t e = euler ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pf_probe_kernel<UKM_OP_INTER, true>, PF_NT_EULER, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pf_probe_kernel<UKM_OP_DIFF, true, true>, PF_NT, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 2;
-        slots_cache[euler].store(per_cu * c->num_cu, std::memory_order_relaxed);
-    }
-    const u64 slots = (u64)slots_cache[euler].load(std::memory_order_relaxed);
+    const u64 slots = euler ? ukm_resident_slots(c, slots_cache[1], pf_probe_kernel<UKM_OP_INTER, true>, PF_NT_EULER)
+                            : ukm_resident_slots(c, slots_cache[0], pf_probe_kernel<UKM_OP_DIFF, true, true>, PF_NT);
     const u64 maxl = euler ? 2048ull : (u64)PF_NT * PF_PER;
     u64 L = (lens[0] + slots - 1) / slots;
     L = std::min<u64>(std::max<u64>(L, PF_MINL), maxl);
@@ -533,35 +490,20 @@ int ukm_dev_probe_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
         for (int j = 1; j < S; j++) rest += lens[j];
         if (rest / (u64)(S - 1) / R64 > 16ull * PF_MAXL) return UKM_OK;
     }
-    const size_t ntab = (size_t)3 * S;
-    std::vector<u64> tab(ntab);
-    for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
-        tab[(size_t)2 * S + j] = lens[j];
-    }
-    u64 *d_tab = nullptr;
-    UKM_TRY(ws_alloc_t(c, ntab, &d_tab));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), ntab * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
 
     PfArgs a;
     memset(&a, 0, sizeof(a));
-    a.tab = d_tab;
-    a.S = (u32)S;
+    UKM_TRY(ukm_stream_tab(c, in, &a.tab));
     a.R = (u32)R64;
     a.L = (u32)L;
     a.T = ukm_taxdev(c);
-    u64 *excl = nullptr;
     UKM_TRY(ws_alloc_t(c, ((size_t)a.R + 1) * (S - 1), &a.cuts));
     UKM_TRY(ws_alloc_t(c, (size_t)a.R * L, &a.tmp_k));
     if (tax) UKM_TRY(ws_alloc_t(c, (size_t)a.R * L, &a.tmp_t));
     UKM_TRY(ws_alloc_t(c, (size_t)a.R, &a.cnt));
-    UKM_TRY(ws_alloc_t(c, (size_t)a.R + 1, &excl));
     UKM_TRY(ws_alloc_t(c, 8, &a.ctl));
     UKM_HIP(hipMemsetAsync(a.ctl, 0, 8 * sizeof(u64), c->stream));
-    const u64 ncuts = ((u64)a.R + 1) * (u64)(S - 1);
-    hipLaunchKernelGGL(pf_cuts_kernel, dim3((unsigned)((ncuts + 255) / 256)), dim3(256), 0, c->stream, a);
+    UKM_TRY(ukm_launch_range_cuts(c, RangeCuts{a.tab.keys() + 1, a.tab.lens() + 1, (u32)S - 1, a.R, in.keys[0], L, a.cuts}));
     (void)hipEventRecord(c->ev_k0, c->stream);
     if (op == UKM_OP_INTER) {
         if (tax) hipLaunchKernelGGL((pf_probe_kernel<UKM_OP_INTER, true>), dim3(a.R), dim3(PF_NT_EULER), 0, c->stream, a);
@@ -574,19 +516,17 @@ int ukm_dev_probe_fold(ukm_ctx *c, int op, const u64 *const *keys, const u32 *co
     (void)hipEventRecord(c->ev_k1, c->stream);
     c->evk_valid = true;
     UKM_HIP(hipGetLastError());
-    UKM_TRY(ukm_dev_exclusive_scan_u64(c, a.cnt, excl, a.R, a.ctl));  // ctl[0] = total
-    hipLaunchKernelGGL(pf_gather_kernel, dim3(a.R), dim3(256), 0, c->stream, a.tmp_k, tax ? a.tmp_t : nullptr, a.cnt, excl, out,
-                       tax ? tout : nullptr, out_cap, a.L);
-    UKM_HIP(hipGetLastError());
-    u64 h[2] = {0, 0};
-    UKM_TRY(ukm_read_u64(c, a.ctl, h, 2));
+    RangeGather g;
+    g.src_k = a.tmp_k;
+    g.src_t = a.tmp_t;
+    g.stride = L;
+    g.cnt = a.cnt;
+    g.R = a.R;
+    u64 h[2];
+    UKM_TRY(ukm_range_finish(c, g, a.ctl, o, h));
     if (ukm_env(c, "UKM_FOLD_DEBUG"))
         fprintf(stderr, "[pfold] op=%d S=%d R=%u L=%u slots=%llu tax=%d flags=%llu out=%llu\n", op, S, a.R, a.L, (unsigned long long)slots,
                 (int)tax, (unsigned long long)h[1], (unsigned long long)h[0]);
     if (h[1] != 0) return UKM_OK;  // duplicate / unsorted / empty marker: the routes behind this one handle and report it
-    *n_out = h[0];
-    if (h[0] > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu records, capacity is %llu", (unsigned long long)h[0], (unsigned long long)out_cap);
-    *fallback = false;
-    return UKM_OK;
+    return ukm_route_answer(h[0], o, declined);
 }

@@ -30,6 +30,7 @@
 #include "ukm_device.h"
 #include "ukm_kway.h"
 #include "ukm_punion.h"
+#include "ukm_route.h"
 
 namespace {
 
@@ -93,41 +94,8 @@ __device__ __forceinline__ u64 pu_splitmix(u64 x) {
     return x ^ (x >> 31);
 }
 
-// cuts[r][j] = lower bound of the first base entry of range r in later file j (r = 0: 0, r = R: the file's length).
-// (Bracketing every cut around its interpolated position made the kernel slower in round 3, 1.8 -> 2.9 ms; a two-level
-//  search -- every 64th range, then an interpolated window between two coarse cuts -- measured the same 1.76 ms in round 6:
-//  the kernel is bound by the ~8 cold lines of a search's last levels, which either form still touches.)
-__global__ void pu_cuts_kernel(PuArgs a) {
-    // a block = 16 ranges x 16 files; 16 neighbouring lanes hold one range's cuts in 16 consecutive files: one 128-byte store
-    // (with the threads of a block on 256 ranges of ONE file every store was a line of its own: 1.77 -> 1.63 ms on config 3)
-    const u32 tiles_j = (a.S1 + 15) / 16;
-    const u32 tr = blockIdx.x / tiles_j, tj = blockIdx.x % tiles_j;
-    const u32 j = tj * 16 + (threadIdx.x & 15), r = tr * 16 + (threadIdx.x >> 4);
-    if (j >= a.S1 || r > a.R) return;
-    const u64 len = a.lens[j];
-    u64 res;
-    if (r == 0) {
-        res = 0;
-    } else if (r == a.R) {
-        res = len;
-    } else {
-        const u64 v = a.base[(u64)r * a.range];
-        const auto f = as_global(a.files[j]);
-        u64 lo = 0, hi = len;
-        while (lo < hi) {
-            const u64 mid = (lo + hi) >> 1;
-            if (f[mid] < v) lo = mid + 1; else hi = mid;
-        }
-        res = lo;
-    }
-    a.cuts[(u64)r * a.S1 + j] = res;
-}
-
-static int pu_launch_cuts(ukm_ctx *c, const PuArgs &a) {
-    const u64 blocks = (((u64)a.R + 1 + 15) / 16) * (((u64)a.S1 + 15) / 16);
-    hipLaunchKernelGGL(pu_cuts_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
-    UKM_HIP(hipGetLastError());
-    return UKM_OK;
+static int pu_launch_cuts(ukm_ctx *c, const PuArgs &a) {  // cuts[r][j] = lower bound of base[r range] in later file j
+    return ukm_launch_range_cuts(c, RangeCuts{a.files, a.lens, a.S1, a.R, a.base, a.range, a.cuts});
 }
 
 // heaviest range: records of all later files inside one range (ctl[4] = max over the ranges)
@@ -1704,25 +1672,19 @@ static int pu_new_codes(ukm_ctx *c, PuArgs a, u32 nf, double miss_rate, u64 late
 }
 
 // the share of sampled records that are found in another file (pu_overlap_kernel); the workspace it takes is given back
-static int pu_overlap_share(ukm_ctx *c, const u64 *const *keys, const u64 *lens, int S, double *share) {
+static int pu_overlap_share(ukm_ctx *c, const UkmStreams &in, double *share) {
     *share = 0.0;
     WsMark m = ws_mark(c);
-    std::vector<u64> tab((size_t)2 * S);
-    for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = lens[j];
-    }
-    u64 *d_tab = nullptr, *ctl = nullptr;
-    UKM_TRY(ws_alloc_t(c, tab.size(), &d_tab));
+    StreamTab tab;
+    u64 *ctl = nullptr;
+    UKM_TRY(ukm_stream_tab(c, in, &tab));
     UKM_TRY(ws_alloc_t(c, 8, &ctl));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     UKM_HIP(hipMemsetAsync(ctl, 0, 8 * sizeof(u64), c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
     PuArgs a;
     memset(&a, 0, sizeof(a));
-    a.files = (const u64 *const *)d_tab;
-    a.lens = d_tab + S;
-    a.S1 = (u32)S;
+    a.files = tab.keys();
+    a.lens = tab.lens();
+    a.S1 = (u32)in.S;
     a.ctl = ctl;
     const u32 nsamp = 1u << 14;
     hipLaunchKernelGGL(pu_overlap_kernel, dim3(nsamp / 256), dim3(256), 0, c->stream, a, nsamp);
@@ -1737,8 +1699,8 @@ static int pu_overlap_share(ukm_ctx *c, const u64 *const *keys, const u64 *lens,
 // one attempt with a base set of k0 files; *low_hit: the later files share too little with it (the caller may try more files)
 // ctax (may be null): the file taxid of a stream whose taxids[j] is null
 static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax, u64 *out,
-                          u32 *tout, u64 out_cap, u64 *n_out, bool *fallback, int k0, bool *low_hit, double *hit_rate, const u32 *ctax) {
-    *fallback = true;
+                          u32 *tout, u64 out_cap, u64 *n_out, bool *declined, int k0, bool *low_hit, double *hit_rate, const u32 *ctax) {
+    *declined = true;
     *n_out = 0;
     *low_hit = false;
     if (S < k0 + 1) return UKM_OK;
@@ -1803,9 +1765,10 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
     UKM_TRY(ws_alloc_t(c, cap0 + 1, &base));
     if (tax) UKM_TRY(ws_alloc_t(c, cap0 + 1, &base_tax));
     u64 n0 = 0;
-    bool fb = false;
-    UKM_TRY(ukm_dev_kway(c, UKM_KWAY_UNION, keys, tax ? taxids : nullptr, lens, k0, tax, base, base_tax, cap0, &n0, &fb));
-    if (fb || n0 == 0) return UKM_OK;
+    bool kw_declined = true;
+    UKM_TRY(ukm_dev_kway(c, UkmStreams{keys, tax ? taxids : nullptr, nullptr, lens, k0, tax}, UKM_KWAY_UNION, UkmOut{base, base_tax, cap0, &n0},
+                         &kw_declined));
+    if (kw_declined || n0 == 0) return UKM_OK;
     lap("base");
 
     // (the pipelined plain kernel loads 16-byte pairs: later files of fewer than two records do not go through it -- their
@@ -1833,25 +1796,17 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
             lens_v[(size_t)k0] = 0;
         }
     }
-    // device tables of the later files: [pointers S1][lens S1][TaxId pointers S1][file taxid | its number << 32, S1]
+    // device tables of the later files; their file taxids become taxid | its number << 32 (pu_cte_kernel)
     const int S1all = S - k0;
-    std::vector<u64> tab((size_t)4 * S1all);
     bool any_ct = false;
-    for (int j = 0; j < S1all; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[k0 + j];
-        tab[(size_t)S1all + j] = lens[k0 + j];
-        tab[(size_t)2 * S1all + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[k0 + j] : nullptr);
-        tab[(size_t)3 * S1all + j] = tax ? (u64)ct_v[(size_t)(k0 + j)] : 0ull;
-        any_ct = any_ct || tab[(size_t)3 * S1all + j] != 0;
-    }
-    u64 *d_tab = nullptr, *ctl = nullptr;
-    UKM_TRY(ws_alloc_t(c, tab.size(), &d_tab));
+    for (int j = k0; j < S; j++) any_ct = any_ct || (tax && ct_v[(size_t)j] != 0);
+    StreamTab tab;
+    u64 *ctl = nullptr;
+    UKM_TRY(ukm_stream_tab(c, UkmStreams{keys, taxids, ct_v.data(), lens, S, tax}.from(k0), &tab));
     UKM_TRY(ws_alloc_t(c, 8, &ctl));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     UKM_HIP(hipMemsetAsync(ctl, 0, 8 * sizeof(u64), c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
     if (any_ct) {
-        hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S1all + 255) / 256)), dim3(256), 0, c->stream, d_tab + 3 * (size_t)S1all, (u32)S1all,
+        hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S1all + 255) / 256)), dim3(256), 0, c->stream, tab.file_taxids(), (u32)S1all,
                            ukm_taxdev(c));
         UKM_HIP(hipGetLastError());
     }
@@ -1867,10 +1822,10 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
     // 2. do the later files look like the base set?
     double miss_rate = 0.0;
     {
-        a.files = (const u64 *const *)d_tab;
-        a.lens = d_tab + S1all;
-        a.tfiles = (const u32 *const *)(d_tab + 2 * (size_t)S1all);  // (the sample also looks at the taxids: clade_mode)
-        a.cte = any_ct ? d_tab + 3 * (size_t)S1all : nullptr;
+        a.files = tab.keys();
+        a.lens = tab.lens();
+        a.tfiles = tab.taxids();  // (the sample also looks at the taxids: clade_mode)
+        a.cte = any_ct ? tab.file_taxids() : nullptr;
         a.S1 = (u32)S1all;
         const u32 nsamp = 1u << 16, nf = (u32)std::min(S1all, 16);
         hipLaunchKernelGGL(pu_sample_kernel, dim3(nsamp / 256), dim3(256), 0, c->stream, a, nsamp, nf);
@@ -1881,7 +1836,7 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
         miss_rate = 1.0 - (double)h[2] / (double)h[3];
         a.clade_mode = pu_clade_mode(c, a.tax, tax, h[2], h[6], h[7]);
         if (a.clade_mode && any_ct) {  // (the file taxids' numbers with their clade codes)
-            hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S1all + 255) / 256)), dim3(256), 0, c->stream, d_tab + 3 * (size_t)S1all, (u32)S1all,
+            hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S1all + 255) / 256)), dim3(256), 0, c->stream, tab.file_taxids(), (u32)S1all,
                                a.tax, 1u);
             UKM_HIP(hipGetLastError());
         }
@@ -1924,11 +1879,10 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
     }
     for (int s0 = 0; s0 < S1all; s0 += PU_MAXS) {
         const int s1 = std::min(PU_MAXS, S1all - s0);
-        // (the pointer and length rows of a batch are not adjacent in d_tab: lens sits S1all entries behind)
-        a.files = (const u64 *const *)(d_tab + s0);
-        a.lens = d_tab + S1all + s0;
-        a.tfiles = (const u32 *const *)(d_tab + 2 * (size_t)S1all + s0);
-        a.cte = any_ct ? d_tab + 3 * (size_t)S1all + s0 : nullptr;
+        a.files = tab.keys() + s0;
+        a.lens = tab.lens() + s0;
+        a.tfiles = tab.taxids() + s0;
+        a.cte = any_ct ? tab.file_taxids() + s0 : nullptr;
         a.S1 = (u32)s1;
         WsMark mark = ws_mark(c);
         UKM_TRY(ws_alloc_t(c, ((size_t)a.R + 1) * s1, &a.cuts));
@@ -1948,7 +1902,7 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
             if (dbg) fprintf(stderr, "[punion] heaviest range %llu records, average %llu\n", (unsigned long long)heaviest, (unsigned long long)avg);
             if (mode != 2 && heaviest > 64 * avg + 65536) {
                 ws_release(c, mark);
-                return UKM_OK;  // (*fallback is still true; a batch that already ran only produced list entries)
+                return UKM_OK;  // (still declined; a batch that already ran only produced list entries)
             }
             UKM_HIP(hipMemsetAsync(ctl + 4, 0, sizeof(u64), c->stream));
         }
@@ -1976,7 +1930,7 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
             UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu records, capacity is %llu", (unsigned long long)n0, (unsigned long long)out_cap);
         UKM_HIP(hipMemcpyAsync(out, base, n0 * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
         if (tax) UKM_HIP(hipMemcpyAsync(tout, base_tax, n0 * sizeof(u32), hipMemcpyDeviceToDevice, c->stream));
-        *fallback = false;
+        *declined = false;
         return UKM_OK;
     }
     // (with TaxIds: new codes arrive once per range and batch with their fold, unclaimed records one by one: the LCA
@@ -1992,7 +1946,7 @@ static int probe_union_k0(ukm_ctx *c, const u64 *const *keys, const u32 *const *
     // (capacity: the 2-way kernel reports the size it needs)
     UKM_TRY(ukm_dev_setop2(c, UKM_OP_UNION, base, base_tax, n0, mu, mut, nmu, 0, out, tout, out_cap, n_out));
     lap("final");
-    *fallback = false;
+    *declined = false;
     return UKM_OK;
 }
 
@@ -2008,8 +1962,8 @@ static u32 pr_range_for(const ukm_ctx *c, u64 n0) {
 
 // `union` of files that carry ONE taxid each (ctax[j]; pr_probe_kernel).  Same contract as probe_union_k0.
 static int probe_union_ranked(ukm_ctx *c, const u64 *const *keys_in, const u64 *lens_in, int S, const u32 *ctax, u64 *out, u32 *tout,
-                              u64 out_cap, u64 *n_out, bool *fallback, int k0, bool *low_hit, double *hit_rate) {
-    *fallback = true;
+                              u64 out_cap, u64 *n_out, bool *declined, int k0, bool *low_hit, double *hit_rate) {
+    *declined = true;
     *n_out = 0;
     *low_hit = false;
     if (S < k0 + 1) return UKM_OK;
@@ -2076,9 +2030,10 @@ static int probe_union_ranked(ukm_ctx *c, const u64 *const *keys_in, const u64 *
     u64 *base = nullptr;
     UKM_TRY(ws_alloc_t(c, cap0 + 1, &base));
     u64 n0 = 0;
-    bool fb = false;
-    UKM_TRY(ukm_dev_kway(c, UKM_KWAY_UNION, bkeys.data(), nullptr, blens.data(), k0, false, base, nullptr, cap0, &n0, &fb));
-    if (fb || n0 == 0) return UKM_OK;
+    bool kw_declined = true;
+    UKM_TRY(ukm_dev_kway(c, UkmStreams{bkeys.data(), nullptr, nullptr, blens.data(), k0, false}, UKM_KWAY_UNION, UkmOut{base, nullptr, cap0, &n0},
+                         &kw_declined));
+    if (kw_declined || n0 == 0) return UKM_OK;
     lap("base");
     // 2. device tables.  [0, S): every file in the order lowest rank, highest, second lowest, second highest ... (an entry's
     // interval is then final after its first two or three files); [S, 2S): lengths; [2S, 3S): taxid | rank << 32;
@@ -2228,7 +2183,7 @@ static int probe_union_ranked(ukm_ctx *c, const u64 *const *keys_in, const u64 *
             UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu records, capacity is %llu", (unsigned long long)n0e, (unsigned long long)out_cap);
         UKM_HIP(hipMemcpyAsync(out, base, n0e * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
         UKM_HIP(hipMemcpyAsync(tout, base_tax, n0e * sizeof(u32), hipMemcpyDeviceToDevice, c->stream));
-        *fallback = false;
+        *declined = false;
         return UKM_OK;
     }
     UKM_TRY(ukm_dev_sort(c, a.miss, a.miss_tax, nm, 64));
@@ -2241,12 +2196,17 @@ static int probe_union_ranked(ukm_ctx *c, const u64 *const *keys_in, const u64 *
     lap("list sort");
     UKM_TRY(ukm_dev_setop2(c, UKM_OP_UNION, base, base_tax, n0e, mu, mut, nmu, 0, out, tout, out_cap, n_out));
     lap("final");
-    *fallback = false;
+    *declined = false;
     return UKM_OK;
 }
 
-int ukm_dev_probe_union(ukm_ctx *c, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax, u64 *out,
-                        u32 *tout, u64 out_cap, u64 *n_out, bool *fallback, const u32 *ctax, bool overlap_known) {
+int ukm_dev_probe_union(ukm_ctx *c, const UkmStreams &in, bool overlap_known, const UkmOut &o, bool *declined) {
+    const u64 *const *keys = in.keys;
+    const u32 *const *taxids = in.taxids;
+    const u32 *ctax = in.file_taxids;
+    const u64 *lens = in.lens;
+    const int S = in.S;
+    const bool tax = in.tax;
     // files of the base set: eight, with TaxIds four (the base union pays an LCA per shared code: 8 files of config 3's
     // shape took as long as a third of the probe pass; the codes the later files add are claimed in the tables anyway).
     // When the later files share too little with it, ONE more attempt with four times as many files -- if the first
@@ -2257,13 +2217,13 @@ int ukm_dev_probe_union(ukm_ctx *c, const u64 *const *keys, const u32 *const *ta
     // left to the merges: 46.4 against 38.3.)
     int k0 = tax ? PT_K0 : PU_K0;
     if (ukm_env(c, "UKM_PUNION_K0")) k0 = std::max(3, std::min(64, atoi(ukm_env(c, "UKM_PUNION_K0"))));  // developer knob
-    *fallback = true;
-    *n_out = 0;
+    *declined = true;
+    *o.n = 0;
     if (ukm_punion_mode(c) < 1 && S >= 2 && !overlap_known) {  // (overlap_known: the caller has just taken this sample itself)
         // files that share next to nothing (a record of one is in another with less than 3 % probability: even 32 of them
         // would cover too little): one small kernel says so before a base set is built
         double share = 0.0;
-        UKM_TRY(pu_overlap_share(c, keys, lens, S, &share));
+        UKM_TRY(pu_overlap_share(c, in, &share));
         if (share < 0.03) return UKM_OK;
     }
     // every file carries ONE taxid: the ranked pass (its base set is a plain union: eight files)
@@ -2276,28 +2236,36 @@ int ukm_dev_probe_union(ukm_ctx *c, const u64 *const *keys, const u32 *const *ta
         double hit = 0.0;
         WsMark m = ws_mark(c);
         c->stat_punion_attempts++;
-        const int rc = ranked ? probe_union_ranked(c, keys, lens, S, ctax, out, tout, out_cap, n_out, fallback, k0, &low_hit, &hit)
-                              : probe_union_k0(c, keys, taxids, lens, S, tax, out, tout, out_cap, n_out, fallback, k0, &low_hit, &hit, ctax);
-        if (rc != UKM_OK || !*fallback || !low_hit) return rc;
+        const int rc = ranked ? probe_union_ranked(c, keys, lens, S, ctax, o.keys, o.taxids, o.cap, o.n, declined, k0, &low_hit, &hit)
+                              : probe_union_k0(c, keys, taxids, lens, S, tax, o.keys, o.taxids, o.cap, o.n, declined, k0, &low_hit, &hit, ctax);
+        if (rc != UKM_OK || !*declined || !low_hit) return rc;
         ws_release(c, m);
         const double miss4 = (1.0 - hit) * (1.0 - hit) * (1.0 - hit) * (1.0 - hit);
         k0 *= 4;
         if (1.0 - miss4 < (tax ? PT_MIN_HIT : PU_MIN_HIT) || k0 > S / 4) break;
     }
-    *fallback = true;
-    *n_out = 0;
+    *declined = true;
+    *o.n = 0;
     return UKM_OK;
 }
 
 // `common` with a threshold below the number of files by the counting tables of pt_probe_kernel<true>.  first_once: keys[0]
 // is the first file as a sorted, duplicate-free set (ukm_common makes it one: every code of the first file counts once,
 // common.go:232,244); every record of every other file counts (common.go:262-266).  !first_once: every record of every
-// file counts (`merge -d` in its final round = the codes with at least two records, util-sort.go:519-530).  *fallback = true: not this path (few
+// file counts (`merge -d` in its final round = the codes with at least two records, util-sort.go:519-530).  It declines (few
 // or small files, more than PU_MAXS of them, later files that share too little with the first, an unsorted file, a record
 // no table could count): nothing that matters was written and the caller's counting merge answers.
-int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax,
-                         u32 threshold, u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback, bool first_once, const u32 *ctax) {
-    *fallback = true;
+int ukm_dev_probe_common(ukm_ctx *c, const UkmStreams &in, u32 threshold, bool first_once, const UkmOut &o, bool *declined) {
+    const u64 *const *keys = in.keys;
+    const u32 *const *taxids = in.taxids;
+    const u64 *lens = in.lens;
+    const int S = in.S;
+    const bool tax = in.tax;
+    u64 *const out = o.keys;
+    u32 *const tout = o.taxids;
+    const u64 out_cap = o.cap;
+    u64 *const n_out = o.n;
+    *declined = true;
     *n_out = 0;
     const int mode = ukm_punion_mode(c);
     if (mode == 0 || S < 3 || S > PU_MAXS || lens[0] == 0) return UKM_OK;
@@ -2312,29 +2280,19 @@ int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *t
     const bool dbg = ukm_env(c, "UKM_PUNION_DEBUG") != nullptr;
     if (mode < 1) {
         double share = 0.0;
-        UKM_TRY(pu_overlap_share(c, keys, lens, S, &share));
+        UKM_TRY(pu_overlap_share(c, in, &share));
         if (share < 0.03) return UKM_OK;  // (files that share next to nothing: see ukm_dev_probe_union)
     }
-    // device tables of ALL files: [pointers S][lens S][TaxId pointers S][file taxid | its number << 32, S]
-    std::vector<u64> tab((size_t)4 * S);
-    std::vector<u32> ct_v((size_t)S, 0u);
+    // device tables of ALL files; their file taxids become taxid | its number << 32 (pu_cte_kernel)
     bool any_ct = false;
-    for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = lens[j];
-        tab[(size_t)2 * S + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
-        if (tax && ctax && !(taxids && taxids[j])) ct_v[(size_t)j] = ctax[j];
-        tab[(size_t)3 * S + j] = (u64)ct_v[(size_t)j];
-        any_ct = any_ct || ct_v[(size_t)j] != 0;
-    }
-    u64 *d_tab = nullptr, *ctl = nullptr;
-    UKM_TRY(ws_alloc_t(c, tab.size(), &d_tab));
+    for (int j = 0; j < S; j++) any_ct = any_ct || in.file_taxid(j) != 0;
+    StreamTab tab;
+    u64 *ctl = nullptr;
+    UKM_TRY(ukm_stream_tab(c, in, &tab));
     UKM_TRY(ws_alloc_t(c, 8, &ctl));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     UKM_HIP(hipMemsetAsync(ctl, 0, 8 * sizeof(u64), c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
     if (any_ct) {
-        hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, d_tab + 3 * (size_t)S, (u32)S, ukm_taxdev(c));
+        hipLaunchKernelGGL(pu_cte_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, tab.file_taxids(), (u32)S, ukm_taxdev(c));
         UKM_HIP(hipGetLastError());
     }
     PuArgs a;
@@ -2364,13 +2322,13 @@ int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *t
     {
         a.base = keys[0];
         a.base_tax = (tax && taxids) ? const_cast<u32 *>(taxids[0]) : nullptr;  // (read only in this mode)
-        a.base_ct = ct_v[0];
+        a.base_ct = in.file_taxid(0);
         a.n0 = n0 = lens[0];
         a.count0 = 1;
-        a.files = (const u64 *const *)(d_tab + 1);
-        a.lens = d_tab + S + 1;
-        a.tfiles = (const u32 *const *)(d_tab + 2 * (size_t)S + 1);
-        a.cte = any_ct ? d_tab + 3 * (size_t)S + 1 : nullptr;
+        a.files = tab.keys() + 1;
+        a.lens = tab.lens() + 1;
+        a.tfiles = tab.taxids() + 1;
+        a.cte = any_ct ? tab.file_taxids() + 1 : nullptr;
         a.S1 = (u32)(S - 1);
         double rate = 0.0;
         if (first_once) UKM_TRY(hit_rate(&rate));
@@ -2387,30 +2345,31 @@ int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *t
                 WsMark bm = ws_mark(c);
                 UKM_TRY(ws_alloc_t(c, cap0 + 1, &base));
                 if (tax) UKM_TRY(ws_alloc_t(c, cap0 + 1, &base_tax));
-                bool fb = false;
                 // (the k-way union reads a taxid per record: a base file with ONE taxid gets its array)
                 std::vector<const u32 *> bt((size_t)k0, nullptr);
                 for (int j = 0; j < k0 && tax; j++) {
                     bt[(size_t)j] = taxids ? taxids[j] : nullptr;
-                    if (!bt[(size_t)j] && ct_v[(size_t)j] != 0 && lens[j]) {
+                    if (!bt[(size_t)j] && in.file_taxid(j) != 0 && lens[j]) {
                         u32 *t = nullptr;
                         UKM_TRY(ws_alloc_t(c, lens[j], &t));
-                        UKM_TRY(ukm_dev_fill_u32(c, t, lens[j], ct_v[(size_t)j]));
+                        UKM_TRY(ukm_dev_fill_u32(c, t, lens[j], in.file_taxid(j)));
                         bt[(size_t)j] = t;
                     }
                 }
-                UKM_TRY(ukm_dev_kway(c, UKM_KWAY_UNION, keys, tax ? bt.data() : nullptr, lens, k0, tax, base, base_tax, cap0, &n0, &fb));
-                if (fb || n0 == 0) return UKM_OK;
+                bool kw_declined = true;
+                UKM_TRY(ukm_dev_kway(c, UkmStreams{keys, tax ? bt.data() : nullptr, nullptr, lens, k0, tax}, UKM_KWAY_UNION,
+                                     UkmOut{base, base_tax, cap0, &n0}, &kw_declined));
+                if (kw_declined || n0 == 0) return UKM_OK;
                 first = 0;
                 a.base = base;
                 a.base_tax = base_tax;
                 a.base_ct = 0;
                 a.n0 = n0;
                 a.count0 = 0;
-                a.files = (const u64 *const *)d_tab;
-                a.lens = d_tab + S;
-                a.tfiles = (const u32 *const *)(d_tab + 2 * (size_t)S);
-                a.cte = any_ct ? d_tab + 3 * (size_t)S : nullptr;
+                a.files = tab.keys();
+                a.lens = tab.lens();
+                a.tfiles = tab.taxids();
+                a.cte = any_ct ? tab.file_taxids() : nullptr;
                 a.S1 = (u32)S;
                 UKM_TRY(hit_rate(&rate));
                 if (mode == 2 || rate >= PT_MIN_HIT) break;
@@ -2459,7 +2418,7 @@ int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *t
                      (unsigned long long)later, threshold, (unsigned long long)h[0], (unsigned long long)h[1]);
     if (h[1] != 0) return UKM_OK;
     const u64 nm = h[0];
-    *fallback = false;
+    *declined = false;
     *n_out = nm;
     if (nm > out_cap)
         UKM_FAIL(UKM_ERR_CAPACITY, "common: output needs %llu records, capacity is %llu", (unsigned long long)nm, (unsigned long long)out_cap);
@@ -2474,11 +2433,18 @@ int ukm_dev_probe_common(ukm_ctx *c, const u64 *const *keys, const u32 *const *t
 
 int ukm_place_mode(const ukm_ctx *c) { return ukm_env_int(c, "UKM_PLACE", -1); }
 
-// Keep-everything merge by placement (pl_merge_kernel).  *fallback = true: not this path (few or small files, files that
+// Keep-everything merge by placement (pl_merge_kernel).  It declines (few or small files, files that
 // share too little, a duplicate inside a file, an unsorted file): nothing that matters was written.
-int ukm_dev_place_merge(ukm_ctx *c, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax, u64 *out,
-                        u32 *tout, u64 out_cap, u64 *n_out, bool *fallback, const u32 *ctax) {
-    *fallback = true;
+int ukm_dev_place_merge(ukm_ctx *c, const UkmStreams &in, const UkmOut &o, bool *declined) {
+    const u64 *const *keys = in.keys;
+    const u64 *lens = in.lens;
+    const int S = in.S;
+    const bool tax = in.tax;
+    u64 *const out = o.keys;
+    u32 *const tout = o.taxids;
+    const u64 out_cap = o.cap;
+    u64 *const n_out = o.n;
+    *declined = true;
     *n_out = 0;
     const int mode = ukm_place_mode(c);
     if (mode == 0 || S < 3 || S > PU_MAXS) return UKM_OK;
@@ -2501,32 +2467,27 @@ int ukm_dev_place_merge(ukm_ctx *c, const u64 *const *keys, const u32 *const *ta
         fprintf(stderr, "[place] %-10s %8.3f ms\n", what, ms_since(t0));
         t0 = std::chrono::steady_clock::now();
     };
-    // 0. device tables of the files: [pointers S][lens S][TaxId pointers S][offsets of the files' records S][file taxids S]
-    std::vector<u64> tab((size_t)5 * S);
+    // 0. device tables of the files, then the offsets of the files' records S
+    std::vector<u64> rec_off((size_t)S);
     u64 off = 0;
     bool any_ct = false;
     for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = lens[j];
-        tab[(size_t)2 * S + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
-        tab[(size_t)3 * S + j] = off;
-        tab[(size_t)4 * S + j] = (tax && ctax && !(taxids && taxids[j])) ? (u64)ctax[j] : 0ull;
-        any_ct = any_ct || tab[(size_t)4 * S + j] != 0;
+        rec_off[(size_t)j] = off;
+        any_ct = any_ct || in.file_taxid(j) != 0;
         off += lens[j];
     }
-    u64 *d_tab = nullptr, *ctl = nullptr;
-    UKM_TRY(ws_alloc_t(c, tab.size(), &d_tab));
+    StreamTab tab;
+    u64 *ctl = nullptr;
+    UKM_TRY(ukm_stream_tab(c, in, &tab, rec_off.data(), rec_off.size()));
     UKM_TRY(ws_alloc_t(c, 8, &ctl));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     UKM_HIP(hipMemsetAsync(ctl, 0, 8 * sizeof(u64), c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
     PuArgs a;
     memset(&a, 0, sizeof(a));
-    a.files = (const u64 *const *)d_tab;
-    a.lens = d_tab + S;
-    a.tfiles = (const u32 *const *)(d_tab + 2 * (size_t)S);
-    a.rec_off = d_tab + 3 * (size_t)S;
-    a.cte = any_ct ? d_tab + 4 * (size_t)S : nullptr;
+    a.files = tab.keys();
+    a.lens = tab.lens();
+    a.tfiles = tab.taxids();
+    a.rec_off = tab.extra();
+    a.cte = any_ct ? tab.file_taxids() : nullptr;
     a.S1 = (u32)S;
     a.ctl = ctl;
     if (mode < 1) {
@@ -2556,13 +2517,14 @@ int ukm_dev_place_merge(ukm_ctx *c, const u64 *const *keys, const u32 *const *ta
     UKM_TRY(ws_alloc_t(c, cap0 + 1, &base));
     u64 n0 = 0;
     {
-        bool fb = true;
+        bool pu_declined = true;
         WsMark m = ws_mark(c);
-        const int rc = ukm_dev_probe_union(c, keys, nullptr, lens, S, false, base, nullptr, cap0, &n0, &fb, nullptr, mode < 1);
+        const int rc = ukm_dev_probe_union(c, UkmStreams{keys, nullptr, nullptr, lens, S, false}, mode < 1, UkmOut{base, nullptr, cap0, &n0},
+                                           &pu_declined);
         ws_release(c, m);
         if (rc == UKM_ERR_CAPACITY) return UKM_OK;
         UKM_TRY(rc);
-        if (fb || n0 == 0) return UKM_OK;
+        if (pu_declined || n0 == 0) return UKM_OK;
     }
     lap("union");
     if (mode < 1 && S <= 1024) {
@@ -2602,7 +2564,7 @@ int ukm_dev_place_merge(ukm_ctx *c, const u64 *const *keys, const u32 *const *ta
     if (dbg) fprintf(stderr, "[place] S=%d N=%llu n0=%llu R=%u flags=%llu\n", S, (unsigned long long)N, (unsigned long long)n0, a.R,
                      (unsigned long long)h[1]);
     if (h[1] != 0) return UKM_OK;
-    *fallback = false;
+    *declined = false;
     *n_out = N;
     return UKM_OK;
 }

@@ -1314,17 +1314,6 @@ __global__ __launch_bounds__(NT, (TAX ? SR_WAVES_TAX : SR_WAVES_PLAIN)) void sr_
     }
 }
 
-// gather the ranges' slots of a union into the caller's buffer: range r goes to dst + excl[r]
-__global__ void sr_gather_kernel(const u64 *src, const u32 *tsrc, const u64 *slot, const u64 *cnt, const u64 *excl, u64 *dst,
-                                 u32 *tdst, u64 cap) {
-    const u32 r = blockIdx.x;
-    const u64 off = slot[r], n = cnt[r], d0 = excl[r];
-    if (d0 + n > cap) return;  // the host reports UKM_ERR_CAPACITY
-    for (u64 i = threadIdx.x; i < n; i += blockDim.x) dst[d0 + i] = src[off + i];
-    if (tsrc)
-        for (u64 i = threadIdx.x; i < n; i += blockDim.x) tdst[d0 + i] = tsrc[off + i];
-}
-
 template <bool TAX, bool UNION, int NT, int VT, int LOGNT>
 int sr_launch(const SrArgs &a, hipStream_t st) {
     if (a.buckets == 1) hipLaunchKernelGGL((sr_merge_kernel<TAX, UNION, NT, VT, LOGNT, 1>), dim3(a.per_xcd * 8), dim3(NT), 0, st, a);
@@ -1346,10 +1335,15 @@ constexpr int SR_CAP = SR_NT * SR_VT;
 
 int ukm_srmerge_mode(const ukm_ctx *c) { return ukm_env_int(c, "UKM_SRMERGE", -1); }
 
-int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const *taxids, const u64 *lens, int S, bool tax,
-                    u64 *out, u32 *tout, u64 out_cap, u64 *n_out, bool *fallback, u32 threshold) {
-    *fallback = true;
-    *n_out = 0;
+int ukm_dev_srmerge(ukm_ctx *c, const UkmStreams &in, int op, u32 threshold, const UkmOut &o, bool *declined) {
+    *declined = true;
+    *o.n = 0;
+    const int S = in.S;
+    const bool tax = in.tax;
+    const u64 *lens = in.lens;
+    u64 *const out = o.keys;
+    u32 *const tout = o.taxids;
+    const u64 out_cap = o.cap;
     const bool uni = op == UKM_KWAY_UNION;
     const int mode = ukm_srmerge_mode(c);
     if (mode == 0 || S < 2 || S > SR_MAX_STREAMS) return UKM_OK;
@@ -1373,7 +1367,7 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
         UKM_FAIL(UKM_ERR_NO_TAXONOMY, "union: records carry taxids but no taxonomy is loaded");
     if (tax && uni && (c->tax_euler == nullptr || c->tax_node_at == nullptr)) return UKM_OK;
     if (!uni && N > out_cap) {
-        *n_out = N;
+        *o.n = N;
         UKM_FAIL(UKM_ERR_CAPACITY, "merge: output needs %llu records, capacity is %llu", (unsigned long long)N,
                  (unsigned long long)out_cap);
     }
@@ -1396,44 +1390,26 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
     const u32 RP = R + 1;
 
     const bool dbg = ukm_env(c, "UKM_SRMERGE_DEBUG") != nullptr;
-    std::vector<std::pair<const char *, hipEvent_t>> marks;
-    auto mark = [&](const char *name) {
-        if (!dbg) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) == hipSuccess) {
-            (void)hipEventRecord(e, c->stream);
-            marks.emplace_back(name, e);
-        }
-    };
-    auto drop_marks = [&]() {
-        for (auto &m : marks) (void)hipEventDestroy(m.second);
-        marks.clear();
-    };
+    PhaseMarks marks(dbg, c->stream);
+    auto mark = [&](const char *name) { marks.mark(name); };
     mark("start");
 
-    // ---- device tables: [keys S][tax S][len S][sample_base S + 1][seg_base S + 1] ------------------------------------
-    const size_t ntab = (size_t)5 * S + 2;
-    std::vector<u64> tab(ntab);
+    // ---- device tables: the streams, then sample_base S + 1, seg_base S + 1 ------------------------------------------
+    std::vector<u64> extra(sample_base);
     u64 nseg = 0;
     for (int j = 0; j < S; j++) {
-        tab[(size_t)j] = (u64)(uintptr_t)keys[j];
-        tab[(size_t)S + j] = (u64)(uintptr_t)((tax && taxids) ? taxids[j] : nullptr);
-        tab[(size_t)2 * S + j] = lens[j];
-        tab[(size_t)4 * S + 1 + j] = nseg;
+        extra.push_back(nseg);
         nseg += (lens[j] + (u64)CT * CT_SEG - 1) / ((u64)CT * CT_SEG);
     }
-    tab[(size_t)5 * S + 1] = nseg;
-    for (int j = 0; j <= S; j++) tab[(size_t)3 * S + j] = sample_base[(size_t)j];
+    extra.push_back(nseg);
     if (nseg > 0x7FFFFFFFull) return UKM_OK;
-    u64 *d_tab = nullptr;
-    UKM_TRY(ws_alloc_t(c, ntab, &d_tab));
-    UKM_HIP(hipMemcpyAsync(d_tab, tab.data(), ntab * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    UKM_HIP(hipStreamSynchronize(c->stream));  // `tab` is a pageable host buffer of this frame
-    const u64 *const *d_keys = reinterpret_cast<const u64 *const *>(d_tab);
-    const u32 *const *d_tax = reinterpret_cast<const u32 *const *>(d_tab + S);
-    const u64 *d_len = d_tab + 2 * (size_t)S;
-    const u64 *d_sbase = d_tab + 3 * (size_t)S;
-    const u64 *d_segbase = d_tab + 4 * (size_t)S + 1;
+    StreamTab tab;
+    UKM_TRY(ukm_stream_tab(c, in, &tab, extra.data(), extra.size()));
+    const u64 *const *d_keys = tab.keys();
+    const u32 *const *d_tax = tab.taxids();
+    const u64 *d_len = tab.lens();
+    const u64 *d_sbase = tab.extra();
+    const u64 *d_segbase = tab.extra() + (size_t)S + 1;
 
     u64 *ctl = nullptr, *spl = nullptr;
     u64 sample_dups = 0;
@@ -1467,7 +1443,7 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
     }
     mark("cuts");
     const TaxDev taxd = ukm_taxdev(c);
-    const bool clade_able = uni && tax && taxids && taxd.clade8 != nullptr && taxd.pair != nullptr && taxd.euler != nullptr && S >= 2;
+    const bool clade_able = uni && tax && in.taxids && taxd.clade8 != nullptr && taxd.pair != nullptr && taxd.euler != nullptr && S >= 2;
     if (clade_able) {  // (rides on the read-back below)
         hipLaunchKernelGGL(sr_taxsample_kernel, dim3(16), dim3(256), 0, c->stream, d_tax, d_len, (u32)S, taxd, ctl + 4);
         UKM_HIP(hipGetLastError());
@@ -1485,8 +1461,7 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
         // 23.9) and loses its counting phase when buckets overflow (20 copies: 22.5 against 19.7): up to ~2.5 copies.
         sample_dups = fl2[1];
         if (fl & SR_FLAG_UNSORTED) {
-            drop_marks();
-            return UKM_OK;  // *fallback: the caller's general route sorts / reports it
+            return UKM_OK;  // declined: the caller's general route sorts / reports it
         }
     }
     // ---- the merge pass -----------------------------------------------------------------------------------------------
@@ -1497,6 +1472,7 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
         if (tax) UKM_TRY(ws_alloc_t(c, N + 1, &slots_t));
         UKM_TRY(ws_alloc_t(c, (size_t)R + 1, &cnt));
         UKM_TRY(ws_alloc_t(c, (size_t)R + 1, &slot_off));
+        UKM_HIP(hipMemsetAsync(cnt, 0, ((size_t)R + 1) * sizeof(u64), c->stream));  // (a range that gives up writes no count)
     }
     SrArgs a;
     memset(&a, 0, sizeof(a));
@@ -1545,25 +1521,21 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
     c->evk_valid = true;
     UKM_HIP(hipGetLastError());
     mark("merge");
+    RangeGather g;  // (a union: the ranges' slots -> contiguous output)
     if (uni) {
-        u64 *excl = nullptr;
-        UKM_TRY(ws_alloc_t(c, (size_t)R + 1, &excl));
-        UKM_TRY(ukm_dev_exclusive_scan_u64(c, cnt, excl, R, ctl));  // ctl[0] = total
-        hipLaunchKernelGGL(sr_gather_kernel, dim3(R), dim3(256), 0, c->stream, slots_k, tax ? slots_t : nullptr, slot_off, cnt, excl, out,
-                           tout, out_cap);
-        UKM_HIP(hipGetLastError());
-        mark("gather");
+        g.src_k = slots_k;
+        g.src_t = tax ? slots_t : nullptr;
+        g.slot = slot_off;
+        g.cnt = cnt;
+        g.R = R;
     }
-    u64 h[2] = {0, 0};
-    UKM_TRY(ukm_read_u64(c, ctl, h, 2));
+    u64 h[2];
+    UKM_TRY(ukm_range_finish(c, g, ctl, o, h));
+    if (uni) mark("gather");
     if (dbg) {
         fprintf(stderr, "[srmerge] S=%d N=%llu R=%u ns=%llu D=%llu flags=%llu out=%llu :", S, (unsigned long long)N, R,
                 (unsigned long long)ns, (unsigned long long)D, (unsigned long long)h[1], (unsigned long long)(uni ? h[0] : N));
-        for (size_t i = 1; i < marks.size(); i++) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, marks[i - 1].second, marks[i].second);
-            fprintf(stderr, " %s=%.3fms", marks[i].first, ms);
-        }
+        marks.print();
         fprintf(stderr, "\n");
 #ifdef SR_PHASES
         u64 ph[16];
@@ -1574,12 +1546,6 @@ int ukm_dev_srmerge(ukm_ctx *c, int op, const u64 *const *keys, const u32 *const
                 (unsigned long long)ph[5], (unsigned long long)ph[6], (unsigned long long)ph[9], (unsigned long long)ph[10], (unsigned long long)ph[8]);
 #endif
     }
-    drop_marks();
-    if (h[1] & (SR_FLAG_UNSORTED | SR_FLAG_DEGENERATE)) return UKM_OK;  // *fallback stays set
-    *fallback = false;
-    *n_out = uni ? h[0] : N;
-    if (*n_out > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "union: output needs %llu records, capacity is %llu", (unsigned long long)*n_out,
-                 (unsigned long long)out_cap);
-    return UKM_OK;
+    if (h[1] & (SR_FLAG_UNSORTED | SR_FLAG_DEGENERATE)) return UKM_OK;
+    return ukm_route_answer(uni ? h[0] : N, o, declined);
 }

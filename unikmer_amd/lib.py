@@ -20,6 +20,8 @@ PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 F_MIX_TAXID, F_CMP_TAXID = 2, 4
 F_DEVICE_STREAMS = 256   # every stream pointer of an n-way call is a device pointer (no per-pointer driver query)
+# Context.last_route(): which internal route answered the last n-way call (include/unikmer_hip.h: UKM_ROUTE_*)
+ROUTE_NONE, ROUTE_TREE, ROUTE_KWAY, ROUTE_PUNION, ROUTE_SRMERGE, ROUTE_SRCOMMON, ROUTE_PCOMMON, ROUTE_PLACE = range(8)
 
 # every symbol include/unikmer_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
