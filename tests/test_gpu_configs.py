@@ -287,7 +287,7 @@ def test_kway_long_runs_and_multisets(env):
     assert np.array_equal(ctx.common(same, 9), np.unique(base))
 
 
-# ------------------------------------------------------------------- union by LDS hash probes (ukm_punion.hip)
+# ------------------------------------------------------------------- union by LDS hash probes (ukm_probe_union.hip)
 def test_probe_union_pipelined_steps_and_order_check(env, monkeypatch):
     """The plain probe pass as one software pipeline per wave (pu2_probe_kernel, round 6): its steps are 16-byte pairs, a
     slice that does not begin its file starts one record early, a last step of one record is moved back by one, lanes
@@ -336,7 +336,7 @@ def test_probe_union_pipelined_steps_and_order_check(env, monkeypatch):
 
 def test_probe_union_matches_oracle(env, monkeypatch):
     """`union` of many plain sets that overlap heavily: the first eight files become the base set, every later record
-    is one hash probe in the LDS table of its range, misses are sorted and merged in (ukm_punion.hip; the reference
+    is one hash probe in the LDS table of its range, misses are sorted and merged in (ukm_probe_union.hip; the reference
     probes a hash map per k-mer, union.go:186-208).  UKM_PUNION=1 takes the path whatever the size, =2 also without
     the hit-rate guard.  Shapes: config 3's draws over one universe (few misses), a base set of less than one range
     and of many, more later files than one launch holds, later files that share nothing with the base set (every

@@ -301,7 +301,7 @@ def test_probe_paths_file_taxids_new_codes_and_aliases(env, monkeypatch):
 
 @pytest.mark.parametrize("clade", ["0", "1", None])
 def test_probe_tables_clade_mode_per_record_taxids(env, monkeypatch, clade):
-    """Round 5: the probe union's / counting probes' tables with per-record taxids in CLADE MODE (ukm_punion.hip: a record
+    """Round 5: the probe union's / counting probes' tables with per-record taxids in CLADE MODE (ukm_probe_union.hip: a record
     brings the one-byte clade code of its taxid; its 4-byte pre-order number is fetched only while the entry's interval
     lies inside one clade) -- UKM_PUNION_CLADE = 1 forces it, 0 forbids it, unset = the sample decides.  Against the oracle
     on files whose later ones bring new codes (claims), with taxids that are unrelated (a hash of the code over the whole

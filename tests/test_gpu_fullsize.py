@@ -176,7 +176,7 @@ def test_metric_config_2x1e9_with_per_record_taxids_full_size(env, monkeypatch):
 
 def test_config3_union_of_100_files_x_1e8_full_size(env, monkeypatch):
     """BASELINE config 3 on one GPU: 100 sorted files of ~1e8 codes drawn (p = 0.5) from one universe of 2e8.
-    The union — the library's own choice (the hash-probe pass of ukm_punion.hip) AND the k-way streaming merge alone
+    The union — the library's own choice (the hash-probe pass of ukm_probe_union.hip) AND the k-way streaming merge alone
     (UKM_PUNION=0) — must equal (a) the universe elements that are in at least one file, computed with torch from the
     generator's membership bits, and (b) a chain of 99 two-way unions through the tile kernel."""
     torch, bench, lib, ctx, O, dev = env
@@ -226,7 +226,7 @@ def test_config3_union_of_100_files_x_1e8_full_size(env, monkeypatch):
 
 def test_config3_union_with_taxids_full_size(env, monkeypatch):
     """Config 3's files WITH taxids (union.go:195-201: the TaxId of a code is the LCA over every record that carries it),
-    100 x 1e8 records through the hash-probe pass with the TaxId fold in its tables (ukm_punion.hip, route 3).
+    100 x 1e8 records through the hash-probe pass with the TaxId fold in its tables (ukm_probe_union.hip, route 3).
     (a) every record of file f carries that file's taxid (a leaf of the complete 8-ary tree): the expected TaxId of every
     code is computed with torch from the membership bits — the smallest and the largest leaf among the files that hold
     the code, climbed to their common ancestor by the tree's arithmetic; (b) uniformly random taxids: three windows of the
@@ -518,7 +518,7 @@ def test_config4_inter_diff_common_1000_files_x_1e6_full_size(env, monkeypatch, 
         otc = torch.empty(total + 8, dtype=torch.int32, device=dev)
         monkeypatch.setenv("UKM_COMMON_PROBE", "0")
         same(ctx.common(files, nfiles, taxs, out=okc, out_taxids=otc), "common", "counting probes")
-        assert ctx.last_route() == ROUTE_PCOMMON   # (hash probes against the first file with a record count per entry, ukm_punion.hip)
+        assert ctx.last_route() == ROUTE_PCOMMON   # (hash probes against the first file with a record count per entry, ukm_probe_union.hip)
         monkeypatch.delenv("UKM_COMMON_PROBE")
         # one below the number of files: codes that one file lacks survive too
         same(ctx.common(files, nfiles - 1, taxs, out=okc, out_taxids=otc), "common_minus_1", "counting probes")

@@ -1,4 +1,4 @@
-"""The keep-everything merge of many files that share their codes, by PLACEMENT (csrc/ukm_punion.hip, pl_merge_kernel;
+"""The keep-everything merge of many files that share their codes, by PLACEMENT (csrc/ukm_place.hip, pl_merge_kernel;
 `merge` = mergeChunksFile's heap, util-sort.go:196-225,289-351): the distinct codes from the probe union, a count per code
 from one probe pass, every code's run written in one piece, the TaxIds placed eight files at a time -- against a stable
 sort of the concatenation (= the heap's order: equal codes in file order) and the oracle's modes.

@@ -148,7 +148,7 @@ def main():
                                                                   "roofline": roof_hbm(8 * total + 8 * u.numel(), ms, "8 B per input record read + 8 B per output record written"),
                                                                   "roofline_kway_merge_only": roof_hbm(8 * total + 8 * u.numel(), ms_kway, "the same bytes over the k-way merge's time"),
                                                                   "ms_kway_merge_only": ms_kway,
-                                                                  "note": "union by LDS hash probes against the union of the first eight files (ukm_punion.hip); "
+                                                                  "note": "union by LDS hash probes against the union of the first eight files (ukm_probe_union.hip); "
                                                                           "ms_kway_merge_only = the k-way streaming merge (ukm_kway.hip, UKM_PUNION=0), same "
                                                                           "result (size and XOR checksum compared); round 1: 7-level pairwise tree, 78.7 ms"}
         del uk, u
@@ -179,7 +179,7 @@ def main():
                                      "checksum": int(ut[0].sum().item()) ^ int(ut[1].to(torch.int64).sum().item()),
                                      "roofline": roof_hbm(bpr * total + 12 * n_probe, ms_t, "%d B per input record read + 12 B per output record written" % bpr)}
             del taxs, ut
-        entry["note_taxids"] = ("route 3 = the hash-probe pass with the TaxId fold in its LDS tables (ukm_punion.hip, round 4); through the k-way "
+        entry["note_taxids"] = ("route 3 = the hash-probe pass with the TaxId fold in its LDS tables (ukm_probe_union.hip, round 4); through the k-way "
                                 "merge the half-size shape took 106 / 124 ms against 31.5 / 87 ms (tools/c3_tax_bench.py)")
         del files, U, out, outt
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# developer tool (GPU box): config 3's plain union through experimental builds of ukm_punion.hip.  args: TAG ... (base = the built library)
+# developer tool (GPU box): config 3's plain union through experimental builds of ukm_probe_union.hip.  args: TAG ... (base = the built library)
 cd $GRAFT_REPO_ROOT
 for t in "$@"; do
   if [ "$t" = base ]; then L=unikmer_amd/libunikmer_hip.so; else L=unikmer_amd/libukm_exp_$t.so; fi

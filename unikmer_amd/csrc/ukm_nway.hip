@@ -18,7 +18,7 @@
 #include "ukm_device.h"
 #include "ukm_fold.h"
 #include "ukm_kway.h"
-#include "ukm_punion.h"
+#include "ukm_probe.h"
 #include "ukm_pfold.h"
 #include "ukm_srmerge.h"
 
@@ -312,7 +312,7 @@ int try_kway(ukm_ctx *ctx, int op, std::vector<Stream> ss, bool tax, u64 *fk, u3
     const UkmOut o{fk, ft, fcap, n_out};
     if (op == UKM_KWAY_MERGE) {
         // many files that share most of their codes: the records of every code are placed behind one another file by file
-        // (ukm_punion.hip, pl_merge_kernel); it declines for few / small files, files that share little, a duplicate
+        // (ukm_place.hip, pl_merge_kernel); it declines for few / small files, files that share little, a duplicate
         // inside a file, an unsorted file.  (A file with ONE taxid goes in as it is: the kernel writes the scalar.)
         const RouteStreams rs(ss);
         UKM_TRY(attempt(ctx, UKM_ROUTE_PLACE, done, [&](bool *d) { return ukm_dev_place_merge(ctx, rs.view(tax), o, d); }));
@@ -328,7 +328,7 @@ int try_kway(ukm_ctx *ctx, int op, std::vector<Stream> ss, bool tax, u64 *fk, u3
 }
 
 // `union` of many sets by LDS hash probes against the union of the first eight (with TaxIds: four) files
-// (ukm_punion.hip): the shape of an n-file union over related genomes, where after a few files nearly every record is
+// (ukm_probe_union.hip): the shape of an n-file union over related genomes, where after a few files nearly every record is
 // already in the result.  Taken for >= PUNION_MIN_STREAMS streams and >= 2^27 (with TaxIds 2^26) records behind the first eight; the path itself
 // backs out (*done = false, nothing written) when a sample of the later files is not found in the base set, when a
 // stream is unsorted or when its miss list overflows, and the k-way merge below answers.
@@ -830,7 +830,7 @@ int common_body(ukm_ctx *ctx, std::vector<Stream> &ss, u32 threshold, bool tax, 
     if (threshold > 1 && ukm_kway_enabled(ctx) && ss[0].n) {
         // files that share most of their codes with the first: one hash probe per record into tables that hold the
         // first file's codes (and claim what the later files add), a record count and the TaxId fold per entry
-        // (ukm_punion.hip, pt_probe_kernel<true>).  It declines for few / small files, later files that share too
+        // (ukm_probe_union.hip, pt_probe_kernel<true>).  It declines for few / small files, later files that share too
         // little with the first, an unsorted file.
         const RouteStreams rs(ss);
         bool done = false;
@@ -927,7 +927,7 @@ extern "C" int ukm_merge_k_ft(ukm_ctx *ctx, const uint64_t *const *keys, const u
         if (m == UKM_REPEATED && ukm_kway_enabled(ctx)) {
             // -d in the final round = the codes that have at least two records, TaxId = LCA over all of them
             // (util-sort.go:519-530): for many files that share most of their codes the counting hash probes of
-            // ukm_punion.hip with a threshold of two (every record of every file counts); it declines for few / small /
+            // ukm_probe_union.hip with a threshold of two (every record of every file counts); it declines for few / small /
             // unsorted files and files that share little, and the merge + scan below answers.
             const RouteStreams rs(all);
             if (rs.size() >= 3) {

@@ -1,4 +1,4 @@
-// ukm_pfold.hip — `inter` / `diff` over MANY sorted sets by LDS hash probes (round 3, after ukm_punion.hip).
+// ukm_pfold.hip — `inter` / `diff` over MANY sorted sets by LDS hash probes (round 3, after ukm_probe_union.hip).
 // Replaces the per-file loops inter.go:205-286 / diff.go:379-454 like ukm_fold.hip does, for the rules that do not depend
 // on the ORDER of the files:
 //     inter        a code of file 0 survives when every later file has it; TaxId = LCA over all files (inter.go:229-239
@@ -10,7 +10,7 @@
 //
 // ukm_fold.hip keeps the survivors in registers and looks each of them up in every file's slice (a lock-step binary
 // search per survivor per file: bound by dependent-instruction latency, 1.6-1.9 TB/s).  Here the roles are swapped, as in
-// ukm_punion.hip: file 0 is cut into ranges of L <= 1536 records; one workgroup per range puts its records into a
+// ukm_probe_union.hip: file 0 is cut into ranges of L <= 1536 records; one workgroup per range puts its records into a
 // bucketised LDS table (1024 buckets x 4 slots, slot -> record index beside it) and its waves STREAM the slices of the
 // later files, one slice per wave at a time: per record one hash and one 32-byte bucket read; a hit bumps the record's
 // counter (inter: alive = S - 1 hits; diff: any hit kills) and, for inter with taxids, folds the TaxId in with a CAS
@@ -266,7 +266,7 @@ void pf_probe_kernel(PfArgs a) {
                 }
         }
     };
-    // The streaming skeleton of pu2_probe_kernel (ukm_punion.hip, round 6).  A STEP = up to 128 records [lo, hi) of the 128
+    // The streaming skeleton of pu2_probe_kernel (ukm_probe_union.hip, round 6).  A STEP = up to 128 records [lo, hi) of the 128
     // at `ptr` (two per lane; lanes whose pair lies beyond hi - 2 re-read the last pair that fits).  A slice that does not
     // begin its file starts one record early (lo = 1): the pair (f[beg - 1], f[beg]) is then checked inside lane 0 like every
     // other pair, and a last step of one record is moved back by one record the same way -- every load is a 16-byte pair

@@ -1,4 +1,4 @@
-// ukm_route.h — internal: what the device routes of the n-way operations share (ukm_punion.hip, ukm_srmerge.hip,
+// ukm_route.h — internal: what the device routes of the n-way operations share (ukm_probe_union.hip, ukm_srmerge.hip,
 // ukm_kway.hip, ukm_pfold.hip, ukm_fold.hip; their caller is ukm_nway.hip)
 //
 // The route contract.  Every route entry ukm_dev_*(c, in, [its own arguments,] out, &declined):
