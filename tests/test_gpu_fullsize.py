@@ -378,10 +378,14 @@ def test_config2_count_sort_100Mbp_full_size(env, monkeypatch, genomes):
     osorted = O.sort_u64(ow)
     ou = O.unique(osorted)
     doff = torch.from_numpy(off.view(np.int64)).to(dev)
-    for knob in (None, "0"):
-        if knob is None:
-            monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
-        else:
+    # ("L256": strips of 256 positions make a tile of 65,536, one more than the strip kernel's 16-bit histogram counters hold:
+    #  it must not count, and the sort must not be told that it did)
+    for knob in (None, "0", "L256"):
+        monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
+        monkeypatch.delenv("UKM_WIN_STRIP_L", raising=False)
+        if knob == "L256":
+            monkeypatch.setenv("UKM_WIN_STRIP_L", "256")
+        elif knob is not None:
             monkeypatch.setenv("UKM_SORT_LOCAL", knob)
         c = ctx.encode_kmers(bases, doff, 31, canonical=True)
         assert np.array_equal(_np(c), ow), knob                 # window order, every code
@@ -396,6 +400,7 @@ def test_config2_count_sort_100Mbp_full_size(env, monkeypatch, genomes):
         assert np.array_equal(_np(ctx.count(bases, doff, 31, canonical=True)), ou), knob
         assert ctx.stat("sort_fused_hist") == fused0 + (1 if knob is None else 0), knob
     monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
+    monkeypatch.delenv("UKM_WIN_STRIP_L", raising=False)
     del bases, hb, ow, osorted, ou
     # the fixture genomes, twice
     from conftest import MG1655, IAI39, AMUC

@@ -642,6 +642,18 @@ def test_nthash(ctx, O, k):
     assert np.array_equal(got, exp)
 
 
+def _strip_kernel_input():
+    bases = _synth_fasta(1_200_000, SEED + 17).copy()
+    bases[1000:1100] = ord("N")
+    bases[70_000] = ord("n")
+    bases[500_001:500_004] = np.frombuffer(b"acg", dtype=np.uint8)
+    bases[900_000] = ord("R")
+    cuts = np.array([0, 0, 150, 300, 301, 333, 5000, 5000, 65_535, 65_536, 65_600, 262_144, 262_145, 700_000, 1_199_950,
+                     1_200_000], dtype=np.uint64)
+    reads = np.arange(0, 1_200_001, 150, dtype=np.uint64)
+    return bases, cuts, reads
+
+
 @pytest.mark.parametrize("force", ["1", None])
 def test_nthash_scaled_strip_kernel(ctx, O, monkeypatch, force):
     """The rolling strip kernel behind `count -H --scale N` (count.go:361,373-375): every k phase (k mod 4),
@@ -652,14 +664,7 @@ def test_nthash_scaled_strip_kernel(ctx, O, monkeypatch, force):
         monkeypatch.delenv("UKM_NTHASH_STRIP", raising=False)
     else:
         monkeypatch.setenv("UKM_NTHASH_STRIP", force)
-    bases = _synth_fasta(1_200_000, SEED + 17).copy()
-    bases[1000:1100] = ord("N")
-    bases[70_000] = ord("n")
-    bases[500_001:500_004] = np.frombuffer(b"acg", dtype=np.uint8)
-    bases[900_000] = ord("R")
-    cuts = np.array([0, 0, 150, 300, 301, 333, 5000, 5000, 65_535, 65_536, 65_600, 262_144, 262_145, 700_000, 1_199_950,
-                     1_200_000], dtype=np.uint64)
-    reads = np.arange(0, 1_200_001, 150, dtype=np.uint64)
+    bases, cuts, reads = _strip_kernel_input()
     for k in (1, 2, 23, 31, 50, 51, 64):
         for scale in (3, 300, 1000, 20000):
             mh = O.max_hash(scale)
@@ -937,6 +942,57 @@ def test_ticketed_fallback_kernel(O, L, monkeypatch):
     assert np.array_equal(c.setop2(L.OP_INTER, A, B), O.inter([A, B]))
     assert np.array_equal(c.setop2(L.OP_DIFF, A, B), O.diff([A, B]))
     c.close()
+
+
+@pytest.mark.parametrize("family", ["unique", "nthash_strip_on", "nthash_strip_off", "minimizer"])
+def test_ticketed_fallback_other_kernels(O, L, monkeypatch, family):
+    """The ticketed instantiations of the other look-back kernels (unique, the two Scaled ntHash kernels, the minimizer
+    sketch), on the inputs of test_unique_modes, test_nthash_scaled_strip_kernel and test_minimizer."""
+    monkeypatch.setenv("UKM_FORCE_TICKET", "1")
+    if family.startswith("nthash"):
+        monkeypatch.setenv("UKM_NTHASH_STRIP", "1" if family == "nthash_strip_on" else "0")
+    c = L.Context(0)
+    try:
+        if family == "unique":
+            child, parent = synth_tree(depth=5, arity=8)
+            c.taxonomy_load(child, parent)
+            tax, T = O.Taxonomy(child, parent), len(child)
+            for n in (2049, 250_000):
+                rng = np.random.default_rng(n)
+                keys = np.sort(rng.integers(0, max(1, n // 3) + 1, n).astype(np.uint64))
+                tx = taxids_for(np.arange(n, dtype=np.uint64), T)
+                for mode in (L.PLAIN, L.UNIQUE, L.REPEATED, L.REPEATED_CHUNK, L.SINGLETON):
+                    assert np.array_equal(c.unique(keys, mode=mode), O.unique(keys, mode=mode))
+                    gk, gt = c.unique(keys, tx, mode=mode)
+                    ok, ot = O.unique(keys, tx, mode=mode, tax=tax)
+                    assert np.array_equal(gk, ok) and np.array_equal(gt, ot)
+        elif family == "minimizer":
+            for k, w in ((31, 15), (7, 2), (21, 1024)):
+                bases = _synth_fasta(120_000, SEED + 4)
+                cuts = np.array([0, 150, 300, 301, 1024, 2047, 2048 + w, 5000, 5000, 77_777, 120_000], dtype=np.uint64)
+                for circular in (False, True):
+                    got, gpos = c.minimizer(bases, cuts, k, w, circular=circular, with_pos=True)
+                    exp, epos = _oracle_minimizer_records(O, bases, cuts, k, w, circular=circular)
+                    assert np.array_equal(got, exp) and np.array_equal(gpos, epos)
+                mh = O.max_hash(7)
+                exp, _ = _oracle_minimizer_records(O, bases, cuts, k, w, max_hash=mh)
+                assert np.array_equal(c.minimizer(bases, cuts, k, w, max_hash=mh), exp)
+        else:
+            bases, cuts, reads = _strip_kernel_input()
+            for k in (2, 23, 51, 64):
+                for scale in (3, 300, 1000, 20000):
+                    mh = O.max_hash(scale)
+                    for canonical in (True, False):
+                        if scale == 3 and (k not in (23, 51) or not canonical):
+                            continue
+                        got = c.nthash(bases, cuts, k, canonical=canonical, max_hash=mh)
+                        exp = O.count_windows(bases, cuts, k, hashed=True, canonical=canonical, max_hash=mh)
+                        assert np.array_equal(got, exp), (k, scale, canonical)
+                mh = O.max_hash(1000)
+                assert np.array_equal(c.nthash(bases, reads, k, max_hash=mh),
+                                      O.count_windows(bases, reads, k, hashed=True, max_hash=mh))
+    finally:
+        c.close()
 
 
 def test_two_contexts_from_two_threads(O, L):

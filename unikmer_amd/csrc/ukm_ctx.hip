@@ -426,6 +426,49 @@ int ukm_read_u64(ukm_ctx *c, const u64 *dev, u64 *host, int n) {
     return UKM_OK;
 }
 
+int ukm_lb_ctl_alloc(ukm_ctx *c, u64 ntiles, size_t tail, LbCtl *b, u64 *head) {
+    const size_t nstat = lb_status_words(ntiles);
+    u64 *ctl = head;
+    if (head) {
+        UKM_TRY(ws_alloc_t(c, nstat + tail, &b->status));
+        b->zero_from = b->status;
+        b->zero_words = nstat;
+    } else {
+        UKM_TRY(ws_alloc_t(c, LbCtl::HEAD + nstat + tail, &ctl));
+        b->status = ctl + 8;  // (= LbCtl::HEAD)
+        b->zero_from = ctl;
+        b->zero_words = LbCtl::HEAD + nstat;
+    }
+    b->result = ctl;
+    b->ticket = (u32 *)(ctl + 2);
+    b->tail = b->status + nstat;
+    return UKM_OK;
+}
+
+int ukm_lb_ctl_zero(ukm_ctx *c, const LbCtl &b) {
+    UKM_HIP(hipMemsetAsync(b.zero_from, 0, b.zero_words * sizeof(u64), c->stream));
+    return UKM_OK;
+}
+
+int ukm_lb_launch(ukm_ctx *c, const LbCtl &b, const LbLaunch &how, const std::function<int(bool ticket)> &launch, u64 res[2]) {
+    bool ticket = c->setop_force_ticket || how.ticket_first;
+    for (bool first = true;; first = false) {
+        if (!(first && how.first_zeroed)) UKM_TRY(ukm_lb_ctl_zero(c, b));
+        if (how.bracket) (void)hipEventRecord(c->ev_k0, c->stream);
+        UKM_TRY(launch(ticket));
+        if (how.bracket) {
+            (void)hipEventRecord(c->ev_k1, c->stream);
+            c->evk_valid = true;
+        }
+        UKM_HIP(hipGetLastError());
+        UKM_TRY(ukm_read_u64(c, b.result, res, 2));
+        if (!(res[1] & how.watchdog)) return UKM_OK;
+        if (ticket) UKM_FAIL(UKM_ERR_HIP, "%s: look-back watchdog fired in the ticketed kernel", how.err_name);
+        ukm_switch_to_tickets(c, how.warn_name);  // this device does not dispatch workgroups in order: stay on tickets
+        ticket = true;
+    }
+}
+
 extern "C" int ukm_last_call_ms(ukm_ctx *c, float *ms) {
     if (!c || !ms) UKM_FAIL(UKM_ERR_INVALID, "ukm_last_call_ms: NULL argument");
     if (!c->ev_valid) UKM_FAIL(UKM_ERR_INVALID, "ukm_last_call_ms: no completed call");

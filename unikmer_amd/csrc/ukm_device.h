@@ -83,9 +83,7 @@ __device__ __forceinline__ u32 block_excl_scan_u32(u32 v, u32 *smem, u32 *total)
 //  * predecessors publish roughly in tile order, so the NEAREST one is the last to become
 //    visible: one lane polls that single word (with a real s_sleep) and the 64-wide read is
 //    issued only once it is there.
-#ifndef LB_STRIDE
-#define LB_STRIDE 8
-#endif
+// (LB_STRIDE and lb_status_words: ukm_internal.h, beside the control block that holds the lines)
 #ifndef LB_W
 #define LB_W 1
 #endif
@@ -98,8 +96,6 @@ __device__ __forceinline__ u32 block_excl_scan_u32(u32 v, u32 *smem, u32 *total)
 #define LB_AGG (1ull << 62)
 #define LB_INCL (2ull << 62)
 #define LB_VAL ((1ull << 62) - 1)
-
-static inline size_t lb_status_words(u64 ntiles) { return (size_t)ntiles * LB_STRIDE; }
 
 __device__ __forceinline__ void lb_store(u64 *p, u64 v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -201,6 +197,39 @@ __device__ __forceinline__ u64 lb_resolve(u64 *status, u64 tile, u64 agg, int la
 __device__ __forceinline__ u64 lb_lookback(u64 *status, u64 tile, u64 agg) {
     if (lane_id() == 0) lb_publish(status, tile, agg);
     return lb_resolve(status, tile, agg, lane_id(), nullptr);
+}
+
+// ---- the launch protocol around the look-back (host side: LbCtl / ukm_lb_launch, ukm_internal.h) ----------------
+// The tile a workgroup works on; every thread calls it, first thing.  TICKET = false: blockIdx.x -- no atomic in
+// front of the tile's loads, but a tile's predecessors are running or done only if the hardware dispatches
+// workgroups in increasing order (observed on MI355X), so lb_resolve keeps its watchdog and the host repeats the
+// launch with TICKET = true when it fires.  TICKET = true: the next value of the counter at `ticket` (zero before
+// the launch), handed round through *slot (LDS) -- live for any dispatch order.  Contains a barrier when TICKET.
+template <bool TICKET>
+__device__ __forceinline__ u64 lb_tile_id(u32 *ticket, u64 *slot) {
+    u64 tile = blockIdx.x;
+    if (TICKET) {
+        if (threadIdx.x == 0) *slot = (u64)atomicAdd(ticket, 1u);
+        __syncthreads();
+        tile = *slot;
+    }
+    return tile;
+}
+
+// Every thread calls it where a kernel has nothing to do between publishing its tile's count and needing its
+// base: the first wave publishes and resolves, a watchdog timeout raises bit `watchdog` in *flags, and the base
+// reaches the whole workgroup through *slot (LDS) and the barrier.  (tid, lane: the caller's threadIdx.x and lane_id().)
+template <bool TICKET>
+__device__ __forceinline__ u64 lb_tile_base(u64 *status, u64 tile, u64 tile_total, u64 *flags, u64 watchdog, u64 *slot, int tid, int lane) {
+    if (tid < 64) {
+        bool timed_out = false;
+        if (lane == 0) lb_publish(status, tile, tile_total);
+        const u64 base = lb_resolve(status, tile, tile_total, lane, TICKET ? nullptr : &timed_out);
+        if (tid == 0) *slot = base;
+        if (timed_out && lane == 0) atomicOr((unsigned long long *)flags, (unsigned long long)watchdog);
+    }
+    __syncthreads();
+    return *slot;
 }
 
 // ---- device LCA (contract: include/unikmer_hip.h, ukm_taxonomy_load) ---------------------------

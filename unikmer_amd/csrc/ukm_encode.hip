@@ -109,6 +109,8 @@ __device__ __forceinline__ void base_tables_init(BaseTables &t, int tid) {
     }
 }
 
+enum : u64 { ENC_FLAG_ILLEGAL = 1, ENC_FLAG_TIMEOUT = 2, ENC_FLAG_OVERFLOW = 4 };  // result word [1] of every kernel here
+
 struct WinArgs {
     const u8 *bases;
     const u64 *rec_off;  // [n_rec + 1]
@@ -123,7 +125,7 @@ struct WinArgs {
     u64 out_cap;
     u64 *status;  // FILTER only
     u32 *ticket;  // FILTER only
-    u64 *result;  // [0] total (FILTER), [1] flags: bit0 = illegal base inside an emitted window
+    u64 *result;  // [0] total (FILTER), [1] flags: ENC_FLAG_ILLEGAL = illegal base inside an emitted window
     u64 ntiles;
     const u64 *tile_rec;  // [ntiles + 3]: record containing position min(t * WT, total_bases - 1)
 };
@@ -207,12 +209,7 @@ __global__ __launch_bounds__(NT) void window_kernel(WinArgs p) {
     __shared__ BaseTables s_t;
     const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
     base_tables_init(s_t, tid);  // visible after the first barrier below
-    u64 tile = blockIdx.x;
-    if (TICKET) {
-        if (tid == 0) s_misc[0] = (u64)atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        tile = s_misc[0];
-    }
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     const u64 P0 = tile * (u64)WT;
     const int k = p.k;
     // ---- stage bases [P0, P0 + TBX) into LDS -----------------------------------------------------
@@ -402,7 +399,7 @@ __global__ __launch_bounds__(NT) void window_kernel(WinArgs p) {
             if (oi < p.out_cap) p.out[oi] = v;
         }
     }
-    if (illegal) atomicOr((unsigned long long *)&p.result[1], 1ull);
+    if (illegal) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)ENC_FLAG_ILLEGAL);
 
     if (FILTER) {
         // survivors in window order: (round j, wave, lane)
@@ -423,15 +420,7 @@ __global__ __launch_bounds__(NT) void window_kernel(WinArgs p) {
         }
         __syncthreads();
         const u32 tile_total = s_cnt[WPT * NWV];
-        if (tid < 64) {
-            bool timed_out = false;
-            if (lane == 0) lb_publish(p.status, tile, (u64)tile_total);
-            const u64 base = lb_resolve(p.status, tile, (u64)tile_total, lane, TICKET ? nullptr : &timed_out);
-            if (tid == 0) s_misc[1] = base;
-            if (timed_out && lane == 0) atomicOr((unsigned long long *)&p.result[1], 2ull);
-        }
-        __syncthreads();
-        const u64 base = s_misc[1];
+        const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tile_total, &p.result[1], ENC_FLAG_TIMEOUT, &s_misc[1], tid, lane);
 #pragma unroll
         for (int j = 0; j < WPT; j++)
             if ((keep >> j) & 1u) {
@@ -482,7 +471,7 @@ struct StripArgs {
     u64 out_cap;
     u64 *status;
     u32 *ticket;
-    u64 *result;  // [0] total, [1] flags: bit1 = look-back watchdog, bit2 = candidate list overflow
+    u64 *result;  // [0] total, [1] flags: ENC_FLAG_OVERFLOW = candidate list overflow
     u64 ntiles;
     const u64 *tile_rec;
 };
@@ -545,12 +534,7 @@ __global__ __launch_bounds__(ST_NT) void nthash_strip_kernel(StripArgs p) {
         s_tout[tid] = make_uint4((u32)c2, (u32)(c2 >> 32), (u32)d, (u32)(d >> 32));
         if (tid == 0) s_n = 0;
     }
-    u64 tile = blockIdx.x;
-    if (TICKET) {
-        if (tid == 0) s_misc[0] = (u64)atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        tile = s_misc[0];
-    }
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     __syncthreads();
     const u64 P0 = tile * (u64)ST_NT * (u64)L;
     const u64 s0 = P0 + (u64)tid * (u64)L;  // first window start of this lane
@@ -624,7 +608,7 @@ __global__ __launch_bounds__(ST_NT) void nthash_strip_kernel(StripArgs p) {
     __syncthreads();
     const u32 n_all = s_n;
     const u32 n = n_all < (u32)ST_CAP ? n_all : (u32)ST_CAP;
-    if (n_all > (u32)ST_CAP && tid == 0) atomicOr((unsigned long long *)&p.result[1], 4ull);
+    if (n_all > (u32)ST_CAP && tid == 0) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)ENC_FLAG_OVERFLOW);
     // window order = (owner lane, sequence number)
     {
         u32 tot;
@@ -680,15 +664,7 @@ __global__ __launch_bounds__(ST_NT) void nthash_strip_kernel(StripArgs p) {
     }
     __syncthreads();
     const u32 tile_total = s_cnt[ST_RND * ST_NWV];
-    if (tid < 64) {
-        bool timed_out = false;
-        if (lane == 0) lb_publish(p.status, tile, (u64)tile_total);
-        const u64 base = lb_resolve(p.status, tile, (u64)tile_total, lane, TICKET ? nullptr : &timed_out);
-        if (tid == 0) s_misc[1] = base;
-        if (timed_out && lane == 0) atomicOr((unsigned long long *)&p.result[1], 2ull);
-    }
-    __syncthreads();
-    const u64 base = s_misc[1];
+    const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tile_total, &p.result[1], ENC_FLAG_TIMEOUT, &s_misc[1], tid, lane);
 #pragma unroll
     for (int m = 0; m < ST_RND; m++)
         if ((keep >> m) & 1u) {
@@ -696,6 +672,33 @@ __global__ __launch_bounds__(ST_NT) void nthash_strip_kernel(StripArgs p) {
             if (pos < p.out_cap) p.out[pos] = hv[m];
         }
     if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tile_total;
+}
+
+// ---- host steps the launches below share ------------------------------------------------------------------------
+// tile_rec[ntiles + 3] from the arena, filled by tile_first_rec_kernel for tiles of tile_size positions
+int first_rec_of_tiles(ukm_ctx *c, const u64 *rec_off, u64 n_rec, u64 total, u64 ntiles, u64 tile_size, const u64 **tile_rec) {
+    u64 *tr = nullptr;
+    UKM_TRY(ws_alloc_t(c, ntiles + 3, &tr));
+    hipLaunchKernelGGL(tile_first_rec_kernel, dim3((unsigned)((ntiles + 3 + 255) / 256)), dim3(256), 0, c->stream, rec_off,
+                       n_rec, total, ntiles, tile_size, tr);
+    *tile_rec = tr;
+    return UKM_OK;
+}
+int check_capacity(u64 n, u64 out_cap) {
+    if (n > out_cap)
+        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu values, capacity is %llu", (unsigned long long)n,
+                 (unsigned long long)out_cap);
+    return UKM_OK;
+}
+int check_legal(const u64 res[2]) {
+    if (res[1] & ENC_FLAG_ILLEGAL) UKM_FAIL(UKM_ERR_ILLEGAL_BASE, "illegal base in sequence (kmers.ErrIllegalBase)");
+    return UKM_OK;
+}
+// one workgroup of nt threads per tile, of the kernel's <TICKET = false> or <TICKET = true> instantiation
+template <typename Args>
+int launch_tiles(void (*blockidx_form)(Args), void (*ticket_form)(Args), bool ticket, u64 ntiles, int nt, hipStream_t st, const Args &p) {
+    hipLaunchKernelGGL(ticket ? ticket_form : blockidx_form, dim3((unsigned)ntiles), dim3(nt), 0, st, p);
+    return UKM_OK;
 }
 
 // returns UKM_OK with *done = false when the strip kernel does not apply (or overflowed): the caller then
@@ -721,36 +724,22 @@ int run_strip_filter(ukm_ctx *c, const u8 *bases, const u64 *rec_off, u64 n_rec,
     const u64 tile_pos = (u64)ST_NT * (u64)L;
     const u64 ntiles = (total_bases + tile_pos - 1) / tile_pos;
     if (ntiles > 0x7FFFFFFFull) return UKM_OK;
-    u64 *ctl = nullptr, *tile_rec = nullptr;
-    const size_t nctl = 8 + lb_status_words(ntiles);
-    UKM_TRY(ws_alloc_t(c, nctl, &ctl));
-    UKM_TRY(ws_alloc_t(c, ntiles + 3, &tile_rec));
-    hipLaunchKernelGGL(tile_first_rec_kernel, dim3((unsigned)((ntiles + 3 + 255) / 256)), dim3(256), 0, c->stream, rec_off,
-                       n_rec, total_bases, ntiles, tile_pos, tile_rec);
+    LbCtl blk;
+    UKM_TRY(ukm_lb_ctl_alloc(c, ntiles, 0, &blk));
     StripArgs p;
     memset(&p, 0, sizeof(p));
     p.bases = bases; p.rec_off = rec_off; p.n_rec = n_rec; p.total_bases = total_bases; p.k = k;
     p.canonical = canonical; p.L = L; p.max_hash = max_hash; p.out = out; p.out_cap = out_cap;
-    p.result = ctl; p.ticket = (u32 *)(ctl + 2); p.status = ctl + 8; p.ntiles = ntiles; p.tile_rec = tile_rec;
+    p.result = blk.result; p.ticket = blk.ticket; p.status = blk.status; p.ntiles = ntiles;
+    UKM_TRY(first_rec_of_tiles(c, rec_off, n_rec, total_bases, ntiles, tile_pos, &p.tile_rec));
     u64 res[2] = {0, 0};
-    for (int attempt = c->setop_force_ticket ? 1 : 0; attempt < 2; attempt++) {
-        UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-        (void)hipEventRecord(c->ev_k0, c->stream);
-        if (attempt == 0) hipLaunchKernelGGL(nthash_strip_kernel<false>, dim3((unsigned)ntiles), dim3(ST_NT), 0, c->stream, p);
-        else hipLaunchKernelGGL(nthash_strip_kernel<true>, dim3((unsigned)ntiles), dim3(ST_NT), 0, c->stream, p);
-        (void)hipEventRecord(c->ev_k1, c->stream);
-        c->evk_valid = true;
-        UKM_HIP(hipGetLastError());
-        UKM_TRY(ukm_read_u64(c, ctl, res, 2));
-        if (!(res[1] & 2)) break;
-        if (attempt == 1) UKM_FAIL(UKM_ERR_HIP, "ntHash strip kernel: look-back watchdog fired in the ticketed kernel");
-        ukm_switch_to_tickets(c, "ntHash strip kernel");
-    }
-    if (res[1] & 4) return UKM_OK;  // candidate list overflow: general kernel
+    const LbLaunch how = {"ntHash strip kernel", "ntHash strip kernel", ENC_FLAG_TIMEOUT, true, false, false};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+        return launch_tiles(nthash_strip_kernel<false>, nthash_strip_kernel<true>, ticket, ntiles, ST_NT, c->stream, p);
+    }, res));
+    if (res[1] & ENC_FLAG_OVERFLOW) return UKM_OK;  // candidate list overflow: general kernel
     *n_out = res[0];
-    if (*n_out > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu values, capacity is %llu", (unsigned long long)*n_out,
-                 (unsigned long long)out_cap);
+    UKM_TRY(check_capacity(*n_out, out_cap));
     *done = true;
     return UKM_OK;
 }
@@ -791,7 +780,7 @@ struct SwArgs {
     int canonical;
     int L;                // positions per lane, multiple of 64
     u64 *out;
-    u64 *result;          // [1] flags: bit0 illegal base in an emitted window, bit2 record table overflow
+    u64 *result;          // [1] flags: ENC_FLAG_ILLEGAL in an emitted window, ENC_FLAG_OVERFLOW of the record table
     const u64 *tile_rec;  // [ntiles + 3]
     // ukm_count (round 6): the sort that follows wants the 256-bin histogram of digit (value >> fshift) & 255 of everything this
     // launch writes -- counted here (one LDS atomic per value, 256 global atomics per workgroup) it saves the sort's own
@@ -830,7 +819,7 @@ __global__ __launch_bounds__(SW_NT) __attribute__((amdgpu_waves_per_eu(HASH ? 3 
     const u64 r1 = p.tile_rec[tile + 1];
     const u64 nr = r1 - r0 + 1;  // records r0 .. r1 may hold positions of the tile
     if (nr > (u64)SW_REC) {
-        if (tid == 0) atomicOr((unsigned long long *)&p.result[1], 4ull);
+        if (tid == 0) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)ENC_FLAG_OVERFLOW);
         return;
     }
     const u64 gap_first = p.rec_off[r0] - p.out_off[r0];  // (uniform: scalar loads)
@@ -1048,7 +1037,7 @@ __global__ __launch_bounds__(SW_NT) __attribute__((amdgpu_waves_per_eu(HASH ? 3 
         }
     }
 #undef SW_NEXT_RECORD
-    if (!HASH && illegal) atomicOr((unsigned long long *)&p.result[1], 1ull);
+    if (!HASH && illegal) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)ENC_FLAG_ILLEGAL);
     if (p.fhist) {
         __syncthreads();
         if (tid < 128) {
@@ -1060,10 +1049,11 @@ __global__ __launch_bounds__(SW_NT) __attribute__((amdgpu_waves_per_eu(HASH ? 3 
 }
 
 // returns UKM_OK with *done = false when the strip kernel does not apply (short records, tiny input, a tile
-// with too many records): the caller then runs window_kernel.  `ctl` is the zeroed control block.
+// with too many records): the caller then runs window_kernel.  `blk` is the caller's control block (no look-back here:
+// its two result words).  fhist / fshift (may be null / -1): see SwArgs; *counted says whether the kernel ran with them.
 int run_strip_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, const u64 *out_off, u64 n_rec, int k,
-                      int canonical, u64 *out, u64 total_bases, u64 *ctl, bool *done, u64 *fhist = nullptr, int fshift = -1) {
-    *done = false;
+                      int canonical, u64 *out, u64 total_bases, const LbCtl &blk, bool *done, u64 *fhist, int fshift, bool *counted) {
+    *done = *counted = false;
     const char *fe = ukm_env(c, "UKM_WIN_STRIP");  // developer / test knob: 0 never, 1 whenever it is correct
     const int force = fe ? atoi(fe) : -1;
     if (force == 0) return UKM_OK;
@@ -1087,29 +1077,22 @@ int run_strip_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off
     const u64 tile_pos = (u64)SW_NT * (u64)L;
     const u64 ntiles = (total_bases + tile_pos - 1) / tile_pos;
     if (ntiles > 0x7FFFFFFFull) return UKM_OK;
-    u64 *tile_rec = nullptr;
-    UKM_TRY(ws_alloc_t(c, ntiles + 3, &tile_rec));
-    hipLaunchKernelGGL(tile_first_rec_kernel, dim3((unsigned)((ntiles + 3 + 255) / 256)), dim3(256), 0, c->stream, rec_off,
-                       n_rec, total_bases, ntiles, tile_pos, tile_rec);
     SwArgs p;
     memset(&p, 0, sizeof(p));
     p.bases = bases; p.rec_off = rec_off; p.out_off = out_off; p.n_rec = n_rec; p.total_bases = total_bases;
-    p.k = k; p.canonical = canonical; p.L = L; p.out = out; p.result = ctl; p.tile_rec = tile_rec;
+    p.k = k; p.canonical = canonical; p.L = L; p.out = out; p.result = blk.result;
+    UKM_TRY(first_rec_of_tiles(c, rec_off, n_rec, total_bases, ntiles, tile_pos, &p.tile_rec));
     // (k <= 16 writes the rows a record cuts value by value, without the count; 16-bit counters: a tile of <= 65,535 positions)
-    if (fhist && fshift >= 0 && k >= 17 && tile_pos <= 65535) { p.fhist = fhist; p.fshift = fshift; }
-    (void)hipEventRecord(c->ev_k0, c->stream);
-    if (hash) hipLaunchKernelGGL(stripwin_kernel<true>, dim3((unsigned)ntiles), dim3(SW_NT), 0, c->stream, p);
-    else hipLaunchKernelGGL(stripwin_kernel<false>, dim3((unsigned)ntiles), dim3(SW_NT), 0, c->stream, p);
-    (void)hipEventRecord(c->ev_k1, c->stream);
-    c->evk_valid = true;
-    UKM_HIP(hipGetLastError());
+    if (fhist && fshift >= 0 && k >= 17 && tile_pos <= 65535) { p.fhist = fhist; p.fshift = fshift; *counted = true; }
     u64 res[2] = {0, 0};
-    UKM_TRY(ukm_read_u64(c, ctl, res, 2));
-    if (res[1] & 4) {  // a tile with more records than the table holds: general kernel
-        UKM_HIP(hipMemsetAsync(ctl, 0, 2 * sizeof(u64), c->stream));
+    const LbLaunch how = {"strip window kernel", "strip window kernel", 0, true, false, false};  // (no look-back: one attempt)
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool) {
+        if (hash) hipLaunchKernelGGL(stripwin_kernel<true>, dim3((unsigned)ntiles), dim3(SW_NT), 0, c->stream, p);
+        else hipLaunchKernelGGL(stripwin_kernel<false>, dim3((unsigned)ntiles), dim3(SW_NT), 0, c->stream, p);
         return UKM_OK;
-    }
-    if (res[1] & 1) UKM_FAIL(UKM_ERR_ILLEGAL_BASE, "illegal base in sequence (kmers.ErrIllegalBase)");
+    }, res));
+    if (res[1] & ENC_FLAG_OVERFLOW) return UKM_OK;  // a tile with more records than the table holds: general kernel
+    UKM_TRY(check_legal(res));
     *done = true;
     return UKM_OK;
 }
@@ -1134,7 +1117,7 @@ int run_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, u64 
         *n_out = 0;
     }
     // per-record window counts -> exclusive scan (n_rec + 1 entries: off[n_rec] = total)
-    u64 *cnt = nullptr, *off = nullptr, *ctl = nullptr;
+    u64 *cnt = nullptr, *off = nullptr;
     UKM_TRY(ws_alloc_t(c, n_rec + 1, &cnt));
     UKM_TRY(ws_alloc_t(c, n_rec + 1, &off));
     if (win_off) *win_off = off;
@@ -1142,63 +1125,47 @@ int run_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, u64 
                        rec_off, n_rec, k, circular, cnt);
     const u64 ntiles = (total_bases + WT - 1) / WT;
     const bool filter = hash && max_hash != 0;
-    const size_t nctl = 8 + (filter ? lb_status_words(ntiles) : 0);
-    UKM_TRY(ws_alloc_t(c, nctl, &ctl));
-    UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-    UKM_TRY(ukm_dev_exclusive_scan_u64(c, cnt, off, n_rec + 1, ctl + 3));
+    LbCtl blk;  // (only the filter compacts: no status lines without it)
+    UKM_TRY(ukm_lb_ctl_alloc(c, filter ? ntiles : 0, 0, &blk));
+    u64 *total_dev = blk.result + 3;  // (one of the head's free words; read before the first launch zeroes the block)
+    UKM_TRY(ukm_dev_exclusive_scan_u64(c, cnt, off, n_rec + 1, total_dev));
     u64 total_windows = 0;
-    UKM_TRY(ukm_read_u64(c, ctl + 3, &total_windows));
+    UKM_TRY(ukm_read_u64(c, total_dev, &total_windows));
     if (total_windows == 0) return UKM_OK;
     if (!filter && total_windows > out_cap) {
         *n_out = total_windows;
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu values, capacity is %llu",
-                 (unsigned long long)total_windows, (unsigned long long)out_cap);
+        return check_capacity(total_windows, out_cap);
     }
     if (!circular && !filter) {
         // long records: the rolling strip kernel
-        bool done = false;
+        bool done = false, counted = false;
         const int fsh = (fused && fused->hist) ? ukm_sort_first_shift(c, total_windows, fused->key_bits) : -1;
-        UKM_TRY(run_strip_windows(c, hash, bases, rec_off, off, n_rec, k, canonical, out, total_bases, ctl, &done, fsh >= 0 ? fused->hist : nullptr, fsh));
+        UKM_TRY(run_strip_windows(c, hash, bases, rec_off, off, n_rec, k, canonical, out, total_bases, blk, &done, fsh >= 0 ? fused->hist : nullptr, fsh, &counted));
         if (done) {
             *n_out = total_windows;
-            if (fused && fsh >= 0 && k >= 17) fused->shift = fsh;  // (the conditions under which run_strip_windows handed the histogram on)
+            if (counted) fused->shift = fsh;
             return UKM_OK;
         }
-        if (fused && fsh >= 0) UKM_HIP(hipMemsetAsync(fused->hist, 0, 256 * sizeof(u64), c->stream));  // (a partial count of the launch that gave up)
+        if (counted) UKM_HIP(hipMemsetAsync(fused->hist, 0, 256 * sizeof(u64), c->stream));  // (a partial count of the launch that gave up)
     }
     WinArgs p;
     memset(&p, 0, sizeof(p));
     p.bases = bases; p.rec_off = rec_off; p.out_off = off; p.n_rec = n_rec;
     p.total_bases = total_bases; p.k = k; p.canonical = canonical; p.circular = circular;
     p.max_hash = max_hash; p.out = out; p.out_cap = out_cap;
-    p.result = ctl; p.ticket = (u32 *)(ctl + 2); p.status = ctl + 8; p.ntiles = ntiles;
-    u64 *tile_rec = nullptr;
-    UKM_TRY(ws_alloc_t(c, ntiles + 3, &tile_rec));
-    hipLaunchKernelGGL(tile_first_rec_kernel, dim3((unsigned)((ntiles + 3 + 255) / 256)), dim3(256), 0, c->stream,
-                       rec_off, n_rec, total_bases, ntiles, (u64)WT, tile_rec);
-    p.tile_rec = tile_rec;
+    p.result = blk.result; p.ticket = blk.ticket; p.status = blk.status; p.ntiles = ntiles;
+    UKM_TRY(first_rec_of_tiles(c, rec_off, n_rec, total_bases, ntiles, (u64)WT, &p.tile_rec));
     u64 res[2] = {0, 0};
-    for (int attempt = (filter && c->setop_force_ticket) ? 1 : 0; attempt < 2; attempt++) {
-        if (attempt == 1) UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));  // second try: ticketed
-        (void)hipEventRecord(c->ev_k0, c->stream);
+    const LbLaunch how = {"window kernel", "ntHash filter kernel", filter ? ENC_FLAG_TIMEOUT : 0, true, false, false};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
         if (!hash) hipLaunchKernelGGL((window_kernel<false, false>), dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
         else if (!filter) hipLaunchKernelGGL((window_kernel<true, false>), dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
-        else if (attempt == 0) hipLaunchKernelGGL((window_kernel<true, true, false>), dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
-        else hipLaunchKernelGGL((window_kernel<true, true, true>), dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
-        (void)hipEventRecord(c->ev_k1, c->stream);
-        c->evk_valid = true;
-        UKM_HIP(hipGetLastError());
-        UKM_TRY(ukm_read_u64(c, ctl, res, 2));
-        if (!(res[1] & 2)) break;  // no look-back watchdog
-        if (attempt == 1) UKM_FAIL(UKM_ERR_HIP, "window kernel: look-back watchdog fired in the ticketed kernel");
-        ukm_switch_to_tickets(c, "ntHash filter kernel");  // this device does not dispatch workgroups in order
-    }
-    if (res[1] & 1) UKM_FAIL(UKM_ERR_ILLEGAL_BASE, "illegal base in sequence (kmers.ErrIllegalBase)");
+        else return launch_tiles(window_kernel<true, true, false>, window_kernel<true, true, true>, ticket, ntiles, NT, c->stream, p);
+        return UKM_OK;
+    }, res));
+    UKM_TRY(check_legal(res));
     *n_out = filter ? res[0] : total_windows;
-    if (*n_out > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu values, capacity is %llu",
-                 (unsigned long long)*n_out, (unsigned long long)out_cap);
-    return UKM_OK;
+    return check_capacity(*n_out, out_cap);
 }
 
 
@@ -1251,12 +1218,7 @@ __global__ __launch_bounds__(NT) void minimizer_kernel(MinArgs p) {
     __shared__ u64 s_r[2];
     __shared__ u64 s_misc[2];
     const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    u64 tile = blockIdx.x;  // see window_kernel: a ticket counter serialises every workgroup on one address
-    if (TICKET) {
-        if (tid == 0) s_misc[0] = (u64)atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        tile = s_misc[0];
-    }
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);  // see window_kernel: a ticket counter serialises every workgroup on one address
     const u64 J0 = tile * (u64)MT;
     const int w = p.w;
     const int E = MT + w + 1;  // entries in use
@@ -1394,15 +1356,7 @@ __global__ __launch_bounds__(NT) void minimizer_kernel(MinArgs p) {
     }
     __syncthreads();
     const u32 tile_total = s_cnt[MPT * NWV];
-    if (tid < 64) {
-        bool timed_out = false;
-        if (lane == 0) lb_publish(p.status, tile, (u64)tile_total);
-        const u64 base = lb_resolve(p.status, tile, (u64)tile_total, lane, TICKET ? nullptr : &timed_out);
-        if (tid == 0) s_misc[1] = base;
-        if (timed_out && lane == 0) atomicOr((unsigned long long *)&p.result[1], 2ull);
-    }
-    __syncthreads();
-    const u64 base = s_misc[1];
+    const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tile_total, &p.result[1], ENC_FLAG_TIMEOUT, &s_misc[1], tid, lane);
 #pragma unroll
     for (int jj = 0; jj < MPT; jj++)
         if ((keep >> jj) & 1u) {
@@ -1427,39 +1381,21 @@ int run_minimizer(ukm_ctx *c, const u8 *bases, const u64 *rec_off, u64 n_rec, in
     UKM_TRY(run_windows(c, true, bases, rec_off, n_rec, k, 1, circular, 0, h, total_bases, &n_h, total_bases, &off));
     if (n_h == 0) return UKM_OK;
     const u64 ntiles = (n_h + MT - 1) / MT;
-    u64 *ctl = nullptr, *tile_rec = nullptr;
-    const size_t nctl = 8 + lb_status_words(ntiles);
-    UKM_TRY(ws_alloc_t(c, nctl, &ctl));
-    UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-    UKM_TRY(ws_alloc_t(c, ntiles + 3, &tile_rec));
-    hipLaunchKernelGGL(tile_first_rec_kernel, dim3((unsigned)((ntiles + 3 + 255) / 256)), dim3(256), 0, c->stream,
-                       off, n_rec, n_h, ntiles, (u64)MT, tile_rec);
+    LbCtl blk;
+    UKM_TRY(ukm_lb_ctl_alloc(c, ntiles, 0, &blk));
     MinArgs p;
     memset(&p, 0, sizeof(p));
     p.h = h; p.off = off; p.n_rec = n_rec; p.total = n_h; p.w = w; p.max_hash = max_hash;
     p.out = out; p.out_pos = out_pos; p.out_cap = out_cap;
-    p.result = ctl; p.ticket = (u32 *)(ctl + 2); p.status = ctl + 8; p.ntiles = ntiles; p.tile_rec = tile_rec;
-    u64 res = 0;
-    for (int attempt = c->setop_force_ticket ? 1 : 0; attempt < 2; attempt++) {
-        if (attempt == 1) UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-        (void)hipEventRecord(c->ev_k0, c->stream);
-        if (attempt == 0) hipLaunchKernelGGL(minimizer_kernel<false>, dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
-        else hipLaunchKernelGGL(minimizer_kernel<true>, dim3((unsigned)ntiles), dim3(NT), 0, c->stream, p);
-        (void)hipEventRecord(c->ev_k1, c->stream);
-        c->evk_valid = true;
-        UKM_HIP(hipGetLastError());
-        u64 r2[2];
-        UKM_TRY(ukm_read_u64(c, ctl, r2, 2));
-        res = r2[0];
-        if (!(r2[1] & 2)) break;
-        if (attempt == 1) UKM_FAIL(UKM_ERR_HIP, "minimizer kernel: look-back watchdog fired in the ticketed kernel");
-        ukm_switch_to_tickets(c, "minimizer kernel");
-    }
-    *n_out = res;
-    if (res > out_cap)
-        UKM_FAIL(UKM_ERR_CAPACITY, "output needs %llu values, capacity is %llu", (unsigned long long)res,
-                 (unsigned long long)out_cap);
-    return UKM_OK;
+    p.result = blk.result; p.ticket = blk.ticket; p.status = blk.status; p.ntiles = ntiles;
+    UKM_TRY(first_rec_of_tiles(c, off, n_rec, n_h, ntiles, (u64)MT, &p.tile_rec));
+    u64 res[2] = {0, 0};
+    const LbLaunch how = {"minimizer kernel", "minimizer kernel", ENC_FLAG_TIMEOUT, true, false, false};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+        return launch_tiles(minimizer_kernel<false>, minimizer_kernel<true>, ticket, ntiles, NT, c->stream, p);
+    }, res));
+    *n_out = res[0];
+    return check_capacity(res[0], out_cap);
 }
 
 int windows_entry(ukm_ctx *ctx, bool hash, const uint8_t *bases, const uint64_t *rec_off,

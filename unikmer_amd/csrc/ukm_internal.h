@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -268,12 +269,50 @@ static inline TaxDev ukm_taxdev(const ukm_ctx *c) {
     return t;
 }
 
-// ---- internal device-pointer entry points (all pointers are device pointers) ------------------
-// internal fourth 2-way operation: merge keeping every record (k-way merge tree of ukm_merge_k)
-#define UKM_OP_MERGE_INTERNAL 3
+// ---- launch protocol of the kernels that compact with the decoupled look-back (ukm_device.h) --------------------
+#ifndef LB_STRIDE
+#define LB_STRIDE 8  /* u64 words per tile's status word: a 64-byte line of its own */
+#endif
+static inline size_t lb_status_words(u64 ntiles) { return (size_t)ntiles * LB_STRIDE; }
+
+// The control block of one launch: [0] count, [1] flags, [2] ticket counter, [3..7] the launch's own words, then one
+// status line per tile.  Head and status lines must be zero before the kernel starts; `tail` words behind them are
+// the launch's own and are never zeroed (the set operation's partition points).
+struct LbCtl {
+    static constexpr size_t HEAD = 8;
+    u64 *result = nullptr;
+    u32 *ticket = nullptr;
+    u64 *status = nullptr;
+    u64 *tail = nullptr;
+    u64 *zero_from = nullptr;  // what must be zero before a launch ...
+    size_t zero_words = 0;     // ... the head too, unless it is the caller's
+};
+// ntiles = 0: a launch without look-back (head only).  `head` != null: HEAD zeroed words the caller owns (a chained fold
+// reads them after the arena is gone); status lines and tail still come from the arena.
+int ukm_lb_ctl_alloc(ukm_ctx *c, u64 ntiles, size_t tail, LbCtl *b, u64 *head = nullptr);
+int ukm_lb_ctl_zero(ukm_ctx *c, const LbCtl &b);
+
 // a look-back watchdog fired in a blockIdx-ordered kernel: from now on this context uses the ticketed
 // instantiations (one warning on stderr per context, so that an operator sees the slower mode)
 void ukm_switch_to_tickets(ukm_ctx *c, const char *where);
+
+// The watchdog ladder.  The first attempt takes tile ids from blockIdx -- unless the context is on tickets already or
+// `ticket_first` says that a second attempt could not repair the first (output over input).  If the kernel then reports
+// its watchdog bit in result word [1], the context switches to tickets for good and the launch is repeated ticketed;
+// a watchdog in the ticketed form is an error.  launch(ticket) enqueues the kernel(s) on c->stream.
+struct LbLaunch {
+    const char *err_name;   // what the error of a watchdog in the ticketed form starts with ("setop", "ukm_unique")
+    const char *warn_name;  // what the warning of ukm_switch_to_tickets calls the kernel
+    u64 watchdog;           // the kernel's watchdog bit (0: this launch has no look-back)
+    bool bracket;           // ev_k0 / ev_k1 around the launch: it is the dominant kernel of the call
+    bool ticket_first;
+    bool first_zeroed;      // an earlier kernel of the stream has zeroed the block for the first attempt
+};
+int ukm_lb_launch(ukm_ctx *c, const LbCtl &b, const LbLaunch &how, const std::function<int(bool ticket)> &launch, u64 res[2]);
+
+// ---- internal device-pointer entry points (all pointers are device pointers) ------------------
+// internal fourth 2-way operation: merge keeping every record (k-way merge tree of ukm_merge_k)
+#define UKM_OP_MERGE_INTERNAL 3
 int ukm_dev_setop2(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na, const u64 *b,
                    const u32 *tb, u64 nb, u32 flags, u64 *out, u32 *tout, u64 out_cap,
                    u64 *n_out);

@@ -34,6 +34,8 @@ constexpr int UVT = UNIQ_VT;  // records per thread (half of it for the chunk pr
 #endif
 constexpr int UVT_TAX = UNIQ_VT_TAX;  // with taxids: 12 B per staged record, 80 KB of LDS -> two workgroups per CU instead of one
 
+enum : u32 { UNIQ_FLAG_UNSORTED = 2, UNIQ_FLAG_TIMEOUT = 4 };  // result word [1]
+
 struct UniqArgs {
     const u64 *k;
     const u32 *t;
@@ -43,7 +45,7 @@ struct UniqArgs {
     u64 out_cap;
     u64 *status;
     u32 *ticket;
-    u64 *result;  // [0] total, [1] flags (bit1 = unsorted)
+    u64 *result;  // [0] total, [1] flags
     u64 ntiles;
     TaxDev tax;
     int mode;
@@ -59,8 +61,8 @@ struct UniqArgs {
 //     prefix per tile — no per-thread output arrays, compaction in place over the input tile.
 // CHUNK = the REPEATED_CHUNK protocol (up to two output records per input record).
 // TICKET: tile ids from an atomic counter (always live) instead of blockIdx (no single-address atomic in front
-// of every tile, but look-back liveness then relies on in-order dispatch: watchdog -> flag 4 -> the host re-runs
-// the ticketed instantiation, see ukm_setops.hip).
+// of every tile, but look-back liveness then relies on in-order dispatch: watchdog -> UNIQ_FLAG_TIMEOUT -> the host
+// re-runs the ticketed instantiation: lb_tile_id, ukm_lb_launch).
 #ifndef UNIQ_OWN_N
 #define UNIQ_OWN_N 8
 #endif
@@ -77,12 +79,7 @@ __global__ __launch_bounds__(UNT) void unique_tile_kernel(UniqArgs p) {
     __shared__ u32 s_cnt[VTU * NWU + 1];
     __shared__ u64 s_misc[2];
     const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    u64 tile = blockIdx.x;
-    if (TICKET) {
-        if (tid == 0) s_misc[0] = (u64)atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        tile = s_misc[0];
-    }
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     const u64 i0 = tile * (u64)TILE_U;
     const int cnt_t = (int)((p.n - i0 < (u64)TILE_U) ? (p.n - i0) : (u64)TILE_U);
 
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(UNT) void unique_tile_kernel(UniqArgs p) {
         const u64 k = key[s];
         const u64 prev = s_keys[in ? j : 0], next = s_keys[in ? j + 2 : 0];
         const bool has_prev = gi > 0, has_next = gi + 1 < p.n;
-        if (in && has_prev && prev > k) bad |= 2;
+        if (in && has_prev && prev > k) bad |= UNIQ_FLAG_UNSORTED;
         const bool head = in && (!has_prev || prev != k);
         const bool tail = in && (!has_next || next != k);
         const bool repeated = !tail;
@@ -270,7 +267,7 @@ __global__ __launch_bounds__(UNT) void unique_tile_kernel(UniqArgs p) {
         bool timed_out = false;
         const u64 base = lb_resolve(p.status, tile, (u64)tile_total, lane, TICKET ? nullptr : &timed_out);
         if (tid == 0) s_misc[1] = base;
-        if (timed_out) bad |= 4u;
+        if (timed_out) bad |= UNIQ_FLAG_TIMEOUT;
     }
     if (bad) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)bad);
     __syncthreads();
@@ -303,6 +300,13 @@ __global__ __launch_bounds__(UNT) void unique_tile_kernel(UniqArgs p) {
     if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tile_total;
 }
 
+template <bool TAX, bool CHUNK, int VTU>
+void launch_unique(const UniqArgs &p, hipStream_t st, bool ticket) {
+    const dim3 grid((unsigned)p.ntiles), block(UNT);
+    if (ticket) hipLaunchKernelGGL((unique_tile_kernel<TAX, CHUNK, VTU, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((unique_tile_kernel<TAX, CHUNK, VTU, false>), grid, block, 0, st, p);
+}
+
 __global__ void check_sorted_kernel(const u64 *k, u64 n, u32 *flags) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -327,9 +331,7 @@ __global__ __launch_bounds__(NT) void excl_scan_u64_kernel(const u64 *in, u64 *o
     __shared__ u64 s_w[NT / 64];
     __shared__ u64 s_misc[2];
     const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    if (tid == 0) s_misc[0] = (u64)atomicAdd(ticket, 1u);
-    __syncthreads();
-    const u64 tile = s_misc[0];
+    const u64 tile = lb_tile_id<true>(ticket, &s_misc[0]);
     const u64 i0 = tile * (u64)(NT * SCAN_VT) + (u64)tid * SCAN_VT;
     u64 v[SCAN_VT];
     u64 sum = 0;
@@ -421,12 +423,11 @@ int ukm_dev_exclusive_scan_u64(ukm_ctx *c, const u64 *in, u64 *out, u64 n, u64 *
         return UKM_OK;
     }
     const u64 ntiles = (n + NT * SCAN_VT - 1) / (NT * SCAN_VT);
-    u64 *ctl = nullptr;
-    const size_t nctl = 8 + lb_status_words(ntiles);
-    UKM_TRY(ws_alloc_t(c, nctl, &ctl));
-    UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
+    LbCtl blk;
+    UKM_TRY(ukm_lb_ctl_alloc(c, ntiles, 0, &blk));
+    UKM_TRY(ukm_lb_ctl_zero(c, blk));
     hipLaunchKernelGGL(excl_scan_u64_kernel, dim3((unsigned)ntiles), dim3(NT), 0, c->stream, in, out, n,
-                       ctl + 8, (u32 *)ctl, total_dev, ntiles);
+                       blk.status, blk.ticket, total_dev, ntiles);
     UKM_HIP(hipGetLastError());
     return UKM_OK;
 }
@@ -464,44 +465,28 @@ int ukm_dev_unique_ex(ukm_ctx *c, const u64 *keys, const u32 *taxids, u64 n, int
     p.tax = ukm_taxdev(c);
     p.mode = mode;
     p.threshold = threshold;
-    u64 *ctl = nullptr;
-    const size_t nctl = 8 + lb_status_words(p.ntiles);
-    UKM_TRY(ws_alloc_t(c, nctl, &ctl));
-    UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-    p.result = ctl;
-    p.ticket = (u32 *)(ctl + 2);
-    p.status = ctl + 8;
-    const dim3 grid((unsigned)p.ntiles), block(UNT);
+    LbCtl blk;
+    UKM_TRY(ukm_lb_ctl_alloc(c, p.ntiles, 0, &blk));
+    p.result = blk.result;
+    p.ticket = blk.ticket;
+    p.status = blk.status;
     // a first attempt that times out may already have written part of the output: when the output aliases
     // the input the retry would read damaged data, so in-place calls take the ticketed kernel straight away
     const bool in_place = (out <= keys && keys < out + out_cap) || (keys <= out && out < keys + n);
     u64 res[2] = {0, 0};
-    for (int attempt = (c->setop_force_ticket || in_place) ? 1 : 0; attempt < 2; attempt++) {
-        if (attempt == 1) UKM_HIP(hipMemsetAsync(ctl, 0, nctl * sizeof(u64), c->stream));
-        if (attempt == 0) {
-            if (chunk) {
-                if (tax) hipLaunchKernelGGL((unique_tile_kernel<true, true, UVT_TAX / 2, false>), grid, block, 0, c->stream, p);
-                else hipLaunchKernelGGL((unique_tile_kernel<false, true, UVT / 2, false>), grid, block, 0, c->stream, p);
-            } else {
-                if (tax) hipLaunchKernelGGL((unique_tile_kernel<true, false, UVT_TAX, false>), grid, block, 0, c->stream, p);
-                else hipLaunchKernelGGL((unique_tile_kernel<false, false, UVT, false>), grid, block, 0, c->stream, p);
-            }
+    // (no bracket: the dominant kernel of ukm_count is not this one)
+    const LbLaunch how = {"ukm_unique", "unique kernel", UNIQ_FLAG_TIMEOUT, false, in_place, false};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+        if (chunk) {
+            if (tax) launch_unique<true, true, UVT_TAX / 2>(p, c->stream, ticket);
+            else launch_unique<false, true, UVT / 2>(p, c->stream, ticket);
         } else {
-            if (chunk) {
-                if (tax) hipLaunchKernelGGL((unique_tile_kernel<true, true, UVT_TAX / 2, true>), grid, block, 0, c->stream, p);
-                else hipLaunchKernelGGL((unique_tile_kernel<false, true, UVT / 2, true>), grid, block, 0, c->stream, p);
-            } else {
-                if (tax) hipLaunchKernelGGL((unique_tile_kernel<true, false, UVT_TAX, true>), grid, block, 0, c->stream, p);
-                else hipLaunchKernelGGL((unique_tile_kernel<false, false, UVT, true>), grid, block, 0, c->stream, p);
-            }
+            if (tax) launch_unique<true, false, UVT_TAX>(p, c->stream, ticket);
+            else launch_unique<false, false, UVT>(p, c->stream, ticket);
         }
-        UKM_HIP(hipGetLastError());
-        UKM_TRY(ukm_read_u64(c, p.result, res, 2));
-        if (!(res[1] & 4)) break;
-        if (attempt == 1) UKM_FAIL(UKM_ERR_HIP, "ukm_unique: look-back watchdog fired in the ticketed kernel");
-        ukm_switch_to_tickets(c, "unique kernel");
-    }
-    if (res[1] & 2) UKM_FAIL(UKM_ERR_UNSORTED, "ukm_unique: input stream is not sorted");
+        return UKM_OK;
+    }, res));
+    if (res[1] & UNIQ_FLAG_UNSORTED) UKM_FAIL(UKM_ERR_UNSORTED, "ukm_unique: input stream is not sorted");
     *n_out = res[0];
     if (res[0] > out_cap)
         UKM_FAIL(UKM_ERR_CAPACITY, "ukm_unique: output needs %llu records, capacity is %llu",

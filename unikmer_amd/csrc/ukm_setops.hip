@@ -1106,12 +1106,7 @@ void setop_tile_kernel(SetopArgs p) {
     u64 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     u64 tlast = clock64();
 #endif
-    u64 tile = blockIdx.x;
-    if (TICKET) {
-        if (tid == 0) s_misc[0] = (u64)atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        tile = s_misc[0];
-    }
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     PH(0);
     setop_resolve_sizes(p, (u64)TILE);
     if (tile >= p.ntiles) return;  // chained call: the launch covers the upper bound of |A|
@@ -1365,14 +1360,12 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     p.ctb = ctb;
     if (p.ntiles > 0xFFFFFFFFull) UKM_FAIL(UKM_ERR_INVALID, "setop: input too large");
 
-    // control block: [result 2 x u64 | ticket | pad][status: one 64-byte line per tile][mp ntiles+1]
-    u64 *ctl = nullptr;
-    const size_t nzero = 8 + lb_status_words(p.ntiles);
-    UKM_TRY(ws_alloc_t(c, nzero + p.ntiles + 1, &ctl));
-    p.result = ctl;
-    p.ticket = (u32 *)(ctl + 2);
-    p.status = ctl + 8;
-    p.mp = ctl + nzero;
+    LbCtl blk;  // the partition points behind it
+    UKM_TRY(ukm_lb_ctl_alloc(c, p.ntiles, p.ntiles + 1, &blk));
+    p.result = blk.result;
+    p.ticket = blk.ticket;
+    p.status = blk.status;
+    p.mp = blk.tail;
     if (tax && !rank && defer_form && (op == UKM_OP_UNION || op == UKM_OP_INTER) && !ukm_env_is(c, "UKM_SETOP_FIX", '0')) {
         UKM_TRY(ws_alloc_t(c, (size_t)p.ntiles * FIX_SLOTS, &p.fix));
         UKM_TRY(ws_alloc_t(c, (size_t)p.ntiles, &p.fix_cnt));
@@ -1381,39 +1374,32 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     UKM_TRY(ws_alloc_t(c, (size_t)p.ntiles * 8, &p.dbg));
     UKM_HIP(hipMemsetAsync(p.dbg, 0, (size_t)p.ntiles * 8 * sizeof(u64), c->stream));
 #endif
-    const unsigned pblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
-    // Attempt 0 takes tile ids from blockIdx (fast path); if its watchdog fires, attempt 1
-    // re-runs with ticketed tile ids, which cannot stall whatever the dispatch order is.
-    for (int attempt = c->setop_force_ticket ? 1 : 0; attempt < 2; attempt++) {
-        const bool ticket = attempt == 1;
-        const bool fused_on = !ukm_env_is(c, "UKM_SETOP_FUSED_PART", '0');  // developer knob
-        const bool first = attempt == (c->setop_force_ticket ? 1 : 0);
-        if (first && fused_on && p.ntiles >= 4 * PART_COARSE) {
-            // status lines, control words and both partition levels in one launch
-            const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
-            if (rank) hipLaunchKernelGGL((setop_partition_fused_kernel<true>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, 8u);
-            else hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, 8u);
-            UKM_HIP(hipGetLastError());
+    // The partition points (they survive a repeated launch).  A plain call takes the fused kernel, which also zeroes
+    // the control block for the first attempt.
+    const bool fused = !ukm_env_is(c, "UKM_SETOP_FUSED_PART", '0') && p.ntiles >= 4 * PART_COARSE;  // (developer knob)
+    if (fused) {
+        const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
+        if (rank) hipLaunchKernelGGL((setop_partition_fused_kernel<true>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
+        else hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
+        UKM_HIP(hipGetLastError());
+    } else if (p.ntiles >= 4 * PART_COARSE) {
+        const unsigned cblocks = (unsigned)((p.ntiles / PART_COARSE + 2 + 3) / 4);  // one wave per coarse boundary
+        const unsigned pblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
+        if (rank) {
+            hipLaunchKernelGGL((setop_partition_coop_kernel<true, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
+            hipLaunchKernelGGL((setop_partition_kernel<true, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
         } else {
-        UKM_HIP(hipMemsetAsync(ctl, 0, nzero * sizeof(u64), c->stream));
-        if (first) {
-            if (p.ntiles >= 4 * PART_COARSE) {
-                const unsigned cblocks = (unsigned)((p.ntiles / PART_COARSE + 2 + 3) / 4);  // one wave per coarse boundary
-                if (rank) {
-                    hipLaunchKernelGGL((setop_partition_coop_kernel<true, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-                    hipLaunchKernelGGL((setop_partition_kernel<true, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-                } else {
-                    hipLaunchKernelGGL((setop_partition_coop_kernel<false, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-                    hipLaunchKernelGGL((setop_partition_kernel<false, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-                }
-            } else {
-                const unsigned wblocks = (unsigned)((p.ntiles + 1 + 3) / 4);  // one wave per boundary
-                if (rank) hipLaunchKernelGGL((setop_partition_coop_kernel<true, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-                else hipLaunchKernelGGL((setop_partition_coop_kernel<false, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-            }
+            hipLaunchKernelGGL((setop_partition_coop_kernel<false, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
+            hipLaunchKernelGGL((setop_partition_kernel<false, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
         }
-        }
-        (void)hipEventRecord(c->ev_k0, c->stream);
+    } else {
+        const unsigned wblocks = (unsigned)((p.ntiles + 1 + 3) / 4);  // one wave per boundary
+        if (rank) hipLaunchKernelGGL((setop_partition_coop_kernel<true, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
+        else hipLaunchKernelGGL((setop_partition_coop_kernel<false, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
+    }
+    // (the bracket holds the tile kernel with its CT / fix / gather kernels, not the partition)
+    const LbLaunch how = {"setop", "set-op kernel", FLAG_TIMEOUT, true, false, fused};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
         if (rank) {
             if (tax) launch_op<true, true, NTS, VT_RANK>(op, p, c->stream, ticket);
             else if (ct) launch_op<false, true, NTS, VT_RANK, true>(op, p, c->stream, ticket);
@@ -1426,14 +1412,8 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
             else if (ct) launch_op<false, false, NTS, VT_PLAIN, true>(op, p, c->stream, ticket);
             else launch_op<false, false, NTS, VT_PLAIN>(op, p, c->stream, ticket);
         }
-        (void)hipEventRecord(c->ev_k1, c->stream);
-        c->evk_valid = true;
-        UKM_HIP(hipGetLastError());
-        UKM_TRY(ukm_read_u64(c, p.result, result_host, 2));
-        if (!(result_host[1] & FLAG_TIMEOUT)) break;
-        if (ticket) UKM_FAIL(UKM_ERR_HIP, "setop: look-back watchdog fired in the ticketed kernel");
-        ukm_switch_to_tickets(c, "set-op kernel");  // this device does not dispatch in order: stay on tickets
-    }
+        return UKM_OK;
+    }, result_host));
 #ifdef UKM_PROFILE_PHASES
     {
         std::vector<u64> h((size_t)p.ntiles * 8);
@@ -1474,7 +1454,6 @@ int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_
     p.cta = cta;
     p.ctb = ctb;
     if (p.ntiles == 0) return UKM_OK;
-    u64 *st = nullptr;
     const unsigned pblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
 #ifndef SETOP_LINK_SMALL_TILES
 #define SETOP_LINK_SMALL_TILES 2048
@@ -1482,14 +1461,14 @@ int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_
     // links of up to a few thousand tiles: ONE wave-cooperative partition kernel that also clears the status lines
     // (three launches less per link than memset + two-level partition; a 1000-file fold is launch bound)
     const bool small = p.ntiles < SETOP_LINK_SMALL_TILES;
-    const size_t nstat = lb_status_words(p.ntiles + 1);
-    UKM_TRY(ws_alloc_t(c, nstat + p.ntiles + 1, &st));
+    LbCtl blk;  // the head is the caller's; one status line more than tiles, the partition points behind them
+    UKM_TRY(ukm_lb_ctl_alloc(c, p.ntiles + 1, p.ntiles + 1, &blk, ctl));
     if (small) p.zero_status = (u32)(p.ntiles + 1);  // cleared by the partition kernel: one launch less
-    else UKM_HIP(hipMemsetAsync(st, 0, nstat * sizeof(u64), c->stream));
-    p.result = ctl;
-    p.ticket = (u32 *)(ctl + 2);
-    p.status = st;
-    p.mp = st + nstat;
+    else UKM_TRY(ukm_lb_ctl_zero(c, blk));
+    p.result = blk.result;
+    p.ticket = blk.ticket;
+    p.status = blk.status;
+    p.mp = blk.tail;
     if (!small) {
         const unsigned cblocks = (unsigned)((p.ntiles / PART_COARSE + 2 + 3) / 4);  // one wave per coarse boundary
         hipLaunchKernelGGL((setop_partition_coop_kernel<false, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);

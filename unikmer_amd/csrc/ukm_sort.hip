@@ -126,8 +126,7 @@ struct PassArgs {
     u64 n;
     int shift;
     SW *status;  // [ntiles][256]
-    u32 *ticket;
-    u32 *flags;        // bit0: look-back watchdog fired
+    u32 *ticket;       // tile ids come from this counter, whatever the dispatch order
     const u64 *gbase;  // [256] exclusive digit bases of this pass
     u64 ntiles;
     u64 *next_hist;    // fused mode: [256] digit counts of the NEXT pass, accumulated while this pass scatters (or nullptr)
@@ -215,17 +214,15 @@ __device__ __forceinline__ void match_any_digit(u32 d, u32 &plo, u32 &phi) {
 #ifndef SORT_LB_W
 #define SORT_LB_W 4
 #endif
-#ifndef SORT_TICKET
-#define SORT_TICKET 1
-#endif
-// TICKET = false: tile id = blockIdx.x (see ukm_setops.hip for the liveness argument and the
-// watchdog); TICKET = true: ids from an atomic counter, dispatch-order independent.
+// Tile ids always come from an atomic counter: every predecessor of a running tile is running or done whatever the
+// dispatch order, so the look-back below needs no watchdog and the host reads nothing back (the blockIdx form of
+// ukm_setops.hip would cost a host round trip per pass for its flag).
 #ifdef SORT_WAVES_PER_EU
 #define SORT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SORT_WAVES_PER_EU, SORT_WAVES_PER_EU)))
 #else
 #define SORT_WAVES_ATTR
 #endif
-template <typename SW, bool PAIRS, bool TICKET, int NT_, int VT_>
+template <typename SW, bool PAIRS, int NT_, int VT_>
 __global__ __launch_bounds__(NT_) SORT_WAVES_ATTR void onesweep_kernel(PassArgs<SW> p) {
     constexpr int NT = NT_, NW = NT_ / 64, VT = VT_, TILE = NT_ * VT_;  // NT >= RADIX: thread d < 256 owns digit d
     static_assert(NT_ >= RADIX && NT_ % 64 == 0, "workgroup must cover all digits");
@@ -240,11 +237,11 @@ __global__ __launch_bounds__(NT_) SORT_WAVES_ATTR void onesweep_kernel(PassArgs<
     __shared__ u32 s_tile;
     __shared__ u32 s_nh[RADIX];
     const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    if (TICKET && tid == 0) s_tile = atomicAdd(p.ticket, 1u);
+    if (tid == 0) s_tile = atomicAdd(p.ticket, 1u);
     if (tid < RADIX) s_nh[tid] = 0;
     for (int i = tid; i < NW * RADIX / 2; i += NT) reinterpret_cast<u32 *>(&s_whist[0][0])[i] = 0;
     __syncthreads();
-    const u64 tile = TICKET ? (u64)s_tile : (u64)blockIdx.x;
+    const u64 tile = (u64)s_tile;
     const u64 tbase = tile * (u64)TILE;
     const u32 valid_count = (u32)((p.n - tbase < (u64)TILE) ? (p.n - tbase) : (u64)TILE);
 
@@ -328,7 +325,6 @@ __global__ __launch_bounds__(NT_) SORT_WAVES_ATTR void onesweep_kernel(PassArgs<
     // SORT_LB_W tiles per hop (independent loads in flight together; one hop is a ~1.5 us
     // device-scope round trip, so a one-tile-per-hop walk was latency bound)
     u64 excl = 0;
-    bool timed_out = false;
 #ifdef SORT_ABL_NOLB  // experiment only: plausible but wrong offsets, no look-back
     excl = tile * (u64)real_cnt;
     if (p.gbase[d] + excl + real_cnt > p.n) excl = 0;
@@ -337,7 +333,6 @@ __global__ __launch_bounds__(NT_) SORT_WAVES_ATTR void onesweep_kernel(PassArgs<
     if (tile > 0 && owner) {
 #endif
         long long t = (long long)tile - 1;
-        u32 spins = 0;
         bool done = false;
         while (!done) {
             SW w[SORT_LB_W];
@@ -360,16 +355,11 @@ __global__ __launch_bounds__(NT_) SORT_WAVES_ATTR void onesweep_kernel(PassArgs<
                 }
             }
             t -= used;
-            if (!done && used < SORT_LB_W) {  // hit an unpublished tile: back off, then re-read from it
-                // (ticketed tile ids: every predecessor is running, the wait always ends — no watchdog, the host
-                //  does not look at the flag in that mode)
-                if (!TICKET && ++spins > LB_SPIN_LIMIT) { timed_out = true; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
+            // hit an unpublished tile: back off, then re-read from it (its workgroup is running: the wait always ends)
+            if (!done && used < SORT_LB_W) __builtin_amdgcn_s_sleep(4);
         }
         __hip_atomic_store(st, (SW)(T::INCL | (SW)(excl + real_cnt)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (timed_out) atomicOr(p.flags, 1u);
     if (owner) s_gbase[d] = p.gbase[d] + excl - (u64)dex;
     if (p.next_hist && owner) {
         const u32 c = s_nh[d];  // (complete: at least one barrier lies between the counting and here)
@@ -392,48 +382,33 @@ int run_passes(ukm_ctx *c, u64 *keys, u32 *vals, u64 *tk, u32 *tv, u64 n, int np
     constexpr int TILE = NT_ * VT_;
     const u64 ntiles = (n + TILE - 1) / TILE;
     SW *status = nullptr;
-    u64 *ctl = nullptr;  // [0] ticket, [1] flags
+    u32 *ticket = nullptr;
     UKM_TRY(ws_alloc_t(c, ntiles * RADIX, &status));
-    UKM_TRY(ws_alloc_t(c, 2, &ctl));
+    UKM_TRY(ws_alloc_t(c, 1, &ticket));
     u64 *src_k = keys, *dst_k = tk;
     u32 *src_v = vals, *dst_v = tv;
     for (int i = 0; i < npass; i++) {
-        // Pass i.  The blockIdx-ordered variant is checked per pass (its source buffer is still
-        // intact if the watchdog fired, so only that pass is repeated with tickets).
-        for (int attempt = (c->setop_force_ticket || SORT_TICKET) ? 1 : 0; attempt < 2; attempt++) {
-            const bool ticket = attempt == 1;
-            UKM_HIP(hipMemsetAsync(status, 0, ntiles * RADIX * sizeof(SW), c->stream));
-            UKM_HIP(hipMemsetAsync(ctl, 0, 2 * sizeof(u64), c->stream));
-            PassArgs<SW> p;
-            p.kin = src_k; p.kout = dst_k; p.vin = src_v; p.vout = dst_v;
-            p.n = n; p.shift = shifts[i];
-            p.status = status; p.ticket = (u32 *)ctl; p.flags = (u32 *)(ctl + 1);
-            p.gbase = gbase_dev + (size_t)i * RADIX;
-            p.ntiles = ntiles;
-            p.next_hist = nullptr;
-            p.next_shift = 0;
-            if (fused_hist) {
-                // bases of this pass from its histogram (built by the pre-pass for i = 0, by pass i - 1 otherwise)
-                if (attempt == ((c->setop_force_ticket || SORT_TICKET) ? 1 : 0))
-                    hipLaunchKernelGGL(radix_bases_kernel, dim3(1), dim3(RADIX), 0, c->stream, fused_hist + (size_t)i * RADIX,
-                                       const_cast<u64 *>(p.gbase));
-                if (i + 1 < npass) {
-                    p.next_hist = fused_hist + (size_t)(i + 1) * RADIX;
-                    p.next_shift = shifts[i + 1];
-                }
+        UKM_HIP(hipMemsetAsync(status, 0, ntiles * RADIX * sizeof(SW), c->stream));
+        UKM_HIP(hipMemsetAsync(ticket, 0, sizeof(u32), c->stream));
+        PassArgs<SW> p;
+        p.kin = src_k; p.kout = dst_k; p.vin = src_v; p.vout = dst_v;
+        p.n = n; p.shift = shifts[i];
+        p.status = status; p.ticket = ticket;
+        p.gbase = gbase_dev + (size_t)i * RADIX;
+        p.ntiles = ntiles;
+        p.next_hist = nullptr;
+        p.next_shift = 0;
+        if (fused_hist) {
+            // bases of this pass from its histogram (built by the pre-pass for i = 0, by pass i - 1 otherwise)
+            hipLaunchKernelGGL(radix_bases_kernel, dim3(1), dim3(RADIX), 0, c->stream, fused_hist + (size_t)i * RADIX,
+                               const_cast<u64 *>(p.gbase));
+            if (i + 1 < npass) {
+                p.next_hist = fused_hist + (size_t)(i + 1) * RADIX;
+                p.next_shift = shifts[i + 1];
             }
-            const dim3 grid((unsigned)ntiles), block(NT_);
-            if (ticket) hipLaunchKernelGGL((onesweep_kernel<SW, PAIRS, true, NT_, VT_>), grid, block, 0, c->stream, p);
-            else hipLaunchKernelGGL((onesweep_kernel<SW, PAIRS, false, NT_, VT_>), grid, block, 0, c->stream, p);
-            UKM_HIP(hipGetLastError());
-            if (ticket) break;  // cannot stall
-            u64 fl = 0;
-            UKM_TRY(ukm_read_u64(c, ctl + 1, &fl));
-            if (!(fl & 1)) break;
-            ukm_switch_to_tickets(c, "radix sort pass");  // this device does not dispatch in order
-            if (fused_hist && i + 1 < npass)  // the repeated pass counts the next digit again
-                UKM_HIP(hipMemsetAsync(fused_hist + (size_t)(i + 1) * RADIX, 0, RADIX * sizeof(u64), c->stream));
         }
+        hipLaunchKernelGGL((onesweep_kernel<SW, PAIRS, NT_, VT_>), dim3((unsigned)ntiles), dim3(NT_), 0, c->stream, p);
+        UKM_HIP(hipGetLastError());
         std::swap(src_k, dst_k);
         std::swap(src_v, dst_v);
     }
@@ -1074,8 +1049,8 @@ int ukm_dev_sort_hist(ukm_ctx *c, u64 *keys, u32 *vals, u64 n, int key_bits, con
     if (n >= SORT_FUSED_MIN) {
         // Large inputs: only the FIRST digit's histogram is built by a pass over the keys; every scatter pass counts
         // the next digit on the fly and a 256-thread kernel turns the counts into bases between two passes.  The
-        // histograms never leave the device and the passes take their tile ids from a ticket counter (SORT_TICKET,
-        // no watchdog flag to read back), so a sort with a known key width has no host round trip at all; constant
+        // histograms never leave the device and the passes take their tile ids from a ticket counter (no watchdog
+        // flag to read back), so a sort with a known key width has no host round trip at all; constant
         // digits inside the key width are not detected here.
         u64 *fh = nullptr, *gb = nullptr, *tk = nullptr;
         u32 *tv = nullptr;
