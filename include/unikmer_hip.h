@@ -201,6 +201,35 @@ uint64_t ukm_max_hash(uint64_t scale);
 int ukm_count(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, int k, int canonical,
               int circular, int hashed, uint64_t max_hash, int mode, uint64_t *out, uint64_t out_cap, uint64_t *n_out);
 
+/* ---- k-mers back to the genome: replace the bodies of `unikmer locate` (locate.go:141-289) and `unikmer map` / `uniqs`
+ *      (map.go:116-491 at its default gap settings -x 0 -X 0).  Windows are always CANONICAL (both commands demand the
+ *      canonical flag of their inputs): 2-bit codes when hashed = 0, ntHash v1 when hashed = 1.  bases / rec_off as for
+ *      ukm_encode_kmers; records shorter than k contribute nothing; out_rec indexes the caller's records (skipped ones
+ *      counted).  Errors as ukm_encode_kmers / ukm_nthash give them (UKM_ERR_K, UKM_ERR_ILLEGAL_BASE).  Limits: fewer than
+ *      2^32 windows per call (window indices are the 32-bit payload of the pair sort; UKM_ERR_INVALID above that), fewer
+ *      than 2^32 queries / set codes.
+ *      ukm_locate: q_keys[nq] = the content of the .unik files in file order, neither sorted nor distinct.  Output: one
+ *      entry per (query, window with that code), queries in q_keys order, each code only where it FIRST appears in q_keys
+ *      (locate.go:284 `delete(m, code)`), a query's windows ascending by (record, position).  out_q = index into q_keys,
+ *      out_pos = index of the window in its record (iter.Index()); with circular the windows are the circular iterator's,
+ *      so out_pos + k may exceed the record length (the reference slices a record extended by its first k - 1 bases).
+ *      Upper bound of the output: the number of windows.
+ *      ukm_map: set_keys[n_set] sorted ascending (duplicates tolerated; UKM_ERR_UNSORTED otherwise); genome_off[n_genome + 1]
+ *      groups consecutive records into genomes (genome_off[0] = 0, genome_off[n_genome] = n_rec).  A window is GOOD when its
+ *      code is in the set and -- unless allow_multi -- occurs exactly once among the windows of its genome (map.go:252-257
+ *      "multiple mapped").  Output: every maximal run of consecutive good windows inside one record with
+ *      last - first + k >= min_len (min_len >= 1), as rec, start = first, end = last + k, in record then position order:
+ *      what the state machine of map.go:362-489 emits at -x 0 -X 0.  Context option "map_sorted" (both calls): 0 the windows look
+ *      their codes up in genome order, 1 all (code, window) pairs are sorted first; default: by the size of the set / the
+ *      number of queries. */
+int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, int k, int circular, int hashed,
+               const uint64_t *q_keys, uint64_t nq, uint64_t *out_q, uint32_t *out_rec, uint64_t *out_pos,
+               uint64_t out_cap, uint64_t *n_out);
+int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
+            uint64_t n_genome, int k, int hashed, const uint64_t *set_keys, uint64_t n_set, int allow_multi,
+            uint64_t min_len, uint32_t *out_rec, uint64_t *out_start, uint64_t *out_end, uint64_t out_cap,
+            uint64_t *n_out);
+
 /* ---- sorts: replace sortutil.Uint64s (count.go:581, union.go:274,295, sort.go:463 ...) and
  *      sorts.Quicksort(CodeTaxidSlice) (sort.go:268,331,457).  In place, ascending by code;
  *      pairs are sorted by code only, stably.  key_bits = number of significant low bits

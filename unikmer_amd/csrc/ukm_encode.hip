@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "ukm_device.h"
+#include "ukm_map.h"
 
 namespace {
 
@@ -1435,6 +1436,12 @@ int windows_entry(ukm_ctx *ctx, bool hash, const uint8_t *bases, const uint64_t 
 }
 
 }  // namespace
+
+// run_windows for the library's other files (ukm_map.h)
+int ukm_dev_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, u64 n_rec, int k, int canonical, int circular,
+                    u64 *out, u64 out_cap, u64 *n_out, u64 total_bases, const u64 **win_off) {
+    return run_windows(c, hash, bases, rec_off, n_rec, k, canonical, circular, 0, out, out_cap, n_out, total_bases, win_off);
+}
 
 extern "C" int ukm_encode_kmers(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off,
                                 uint64_t n_rec, int k, int canonical, int circular, uint64_t *out,

@@ -36,6 +36,7 @@ SYMBOLS = [
     "ukm_shard_splitters", "ukm_shard_splitters_plan", "ukm_shard_counts_tax", "ukm_shard_counts_plan", "ukm_count",
     "ukm_ctx_set_option", "ukm_ctx_unset_option", "ukm_ctx_get_option", "ukm_ctx_get_stat",
     "ukm_setop2_ft", "ukm_union_ft", "ukm_inter_ft", "ukm_diff_ft", "ukm_common_ft", "ukm_merge_k_ft",
+    "ukm_locate", "ukm_map",
 ]
 
 
@@ -123,6 +124,8 @@ def load():
     L.ukm_encode_kmers.argtypes = [vp, vp, vp, u64, i32, i32, i32, vp, u64, pu64]
     L.ukm_nthash.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, u64, pu64]
     L.ukm_count.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, u64, i32, vp, u64, pu64]
+    L.ukm_locate.argtypes = [vp, vp, vp, u64, i32, i32, i32, vp, u64, vp, vp, vp, u64, pu64]
+    L.ukm_map.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, vp, u64, i32, u64, vp, vp, vp, u64, pu64]
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -373,6 +376,46 @@ class Context:
 
     def max_hash(self, scale):
         return self.L.ukm_max_hash(scale)
+
+    # ---- k-mers back to the genome ----
+    def _coords(self, call, ref, dtypes, out_cap):
+        """run call(pointers, cap, n) with caller-side outputs of `out_cap` entries; with out_cap None: a first guess, and
+        the exact size the library reports (UKM_ERR_CAPACITY, n_out) for the one repeat"""
+        cap = (1 << 16) if out_cap is None else int(out_cap)
+        for attempt in (0, 1):
+            outs = [_empty_like_kind(ref, cap, dt) for dt in dtypes]
+            n = C.c_uint64()
+            rc = call([_ptr(o, dt)[0] for o, dt in zip(outs, dtypes)], cap, n)
+            if rc == ERR_CAPACITY and out_cap is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc)
+            return tuple(o[: n.value] for o in outs)
+
+    def locate(self, bases, rec_off, k, q_keys, circular=False, hashed=False, out_cap=None):
+        """`unikmer locate` (locate.go:141-289): every occurrence of every queried code.  Returns (q, rec, pos): index into
+        q_keys, record index, window index in the record; queries in q_keys order (a code only where it first appears),
+        a query's windows ascending."""
+        pb, _, k1 = _ptr(bases, np.uint8)
+        poff, noff, k2 = _ptr(rec_off, np.uint64)
+        pq, nq, k3 = _ptr(q_keys, np.uint64)
+        return self._coords(lambda o, cap, n: self.L.ukm_locate(self.h, pb, poff, noff - 1, int(k), int(circular), int(hashed), pq, nq,
+                                                                o[0], o[1], o[2], cap, C.byref(n)),
+                            bases, (np.uint64, np.uint32, np.uint64), out_cap)
+
+    def map(self, bases, rec_off, genome_off, k, set_keys, hashed=False, allow_multi=False, min_len=200, out_cap=None):
+        """`unikmer map` / `uniqs` at -x 0 -X 0 (map.go:116-491): regions covered by k-mers of the sorted set.  Returns
+        (rec, start, end) per region, in record then position order.  genome_off groups records into genomes
+        (None: every record its own genome)."""
+        pb, _, k1 = _ptr(bases, np.uint8)
+        poff, noff, k2 = _ptr(rec_off, np.uint64)
+        if genome_off is None:
+            genome_off = np.arange(noff, dtype=np.uint64)
+        pg, ng, k3 = _ptr(genome_off, np.uint64)
+        ps, ns, k4 = _ptr(set_keys, np.uint64)
+        return self._coords(lambda o, cap, n: self.L.ukm_map(self.h, pb, poff, noff - 1, pg, ng - 1, int(k), int(hashed), ps, ns,
+                                                             int(allow_multi), int(min_len), o[0], o[1], o[2], cap, C.byref(n)),
+                            bases, (np.uint32, np.uint64, np.uint64), out_cap)
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
