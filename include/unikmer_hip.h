@@ -63,6 +63,8 @@ extern "C" {
 /* flags */
 #define UKM_F_MIX_TAXID 2u   /* inter --mix-taxid, inter.go:229-236 */
 #define UKM_F_CMP_TAXID 4u   /* diff -t/--compare-taxid, diff.go:361-362,406-407 */
+#define UKM_F_INVERT 8u      /* grep -v / filter -v: keep the records the predicate rejects */
+#define UKM_F_QUERY_TAXID 16u /* grep -t: the queries are taxids (kept for symmetry: a non-NULL q_taxids already says so) */
 #define UKM_F_DEVICE_STREAMS 256u /* n-way calls (union / inter / diff / common): every keys[i] / taxids[i] is a DEVICE pointer.
                                    * Without it each pointer is classified with hipPointerGetAttributes (host arrays are
                                    * staged), which for a fold over 1000 files is 2000 driver queries = most of the call's
@@ -135,13 +137,16 @@ int ukm_last_route(ukm_ctx *ctx);
  *        route of a 2-way operation with per-record taxids never / for inter / also for union (default: 0 on a taxonomy
  *        with one-byte clade codes, else 1);   "setop_defer" 0 the LCAs of a 2-way union / inter with per-record taxids inside the
  *        merge step instead of densely behind it;   "punion_clade" / "srmerge_clade" 0 / 1
- *        clade codes in the probe tables / the single pass's emit never / always.
+ *        clade codes in the probe tables / the single pass's emit never / always;
+ *        "grep_lds" 0 / 1 ukm_grep by codes: the queries never / whenever they fit (2048 of them) in an LDS table per
+ *        workgroup instead of sorted behind a prefix directory.
  *      The environment is read ONCE, when a context is created: every UKM_* variable present then is the context's default
  *      for the matching key; no compute call calls getenv (a context created under UKM_ENV_LIVE=1 -- the test suite, which
  *      flips knobs between calls -- keeps looking).  An explicitly set option always wins.
  *      ukm_ctx_get_stat: "punion_attempts" = base sets the last hash-probe union / counting-probe call built (2: its retry
  *      with four times the files ran), "workspace_bytes" = device workspace currently held by the context, "sort_fused_hist" = sorts of this context whose first
- *      digit histogram came from the kernel that produced the keys (ukm_count) instead of a pass of their own. */
+ *      digit histogram came from the kernel that produced the keys (ukm_count) instead of a pass of their own, "grep_route" =
+ *      the membership shape of the last ukm_grep (1 LDS table, 2 prefix directory, 3 taxid bitmap, 0 no kernel ran). */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);
@@ -244,6 +249,34 @@ int ukm_sort_pairs(ukm_ctx *ctx, uint64_t *keys, uint32_t *taxids, uint64_t n, i
 int ukm_unique(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n,
                int mode, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap,
                uint64_t *n_out);
+
+/* ---- record selection: replace the record loops of `unikmer grep` (grep.go:617-676), `unikmer filter` (filter.go:130-151 with
+ *      filterCode, filter.go:181-221) and `unikmer sample` (sample.go:134-148).  One predicate per record; the kept records are
+ *      written in INPUT order, every duplicate included, each with its OWN taxid (copied, never folded: no taxonomy is needed).
+ *      The input need not be sorted.  taxids == NULL: nothing is written to out_taxids.  Upper bound of the output: n.  Too small
+ *      an out_cap: UKM_ERR_CAPACITY, *n_out = the size needed.  n == 0 is legal.  Outputs must not alias inputs.
+ *      ukm_grep: exactly one of q_keys[nq] / q_taxids[nq] is non-NULL (both NULL only with nq == 0); the queries are neither
+ *      sorted nor distinct.  q_keys: a record is kept when (its code is among q_keys) XOR UKM_F_INVERT; canonical_k in 1..32
+ *      replaces every record's code by kmers.Canonical(code, k) before the lookup AND in the output (grep.go:641-643),
+ *      canonical_k == 0 (hashed or canonical files) takes the codes as they are.  q_taxids: the test is on the record's taxid
+ *      and the codes are written as they are (grep.go:628-633); with taxids == NULL every record carries file_taxid (what
+ *      unik.Reader.ReadCodeWithTaxid hands out for a file with a global taxid), so the call is a copy or an empty result.
+ *      nq == 0 keeps nothing; inverted, everything.  Fewer than 2^32 queries.
+ *      ukm_filter: the low-complexity filter, exactly filterCode: bases are read from the LOW end of the code,
+ *      scores[0] = penalty_d, scores[i] = penalty_s when base i equals base i - 1 else penalty_d; window > k is clamped to k;
+ *      the sum of `window` scores is tested at positions 0 .. max(k - window - 1, 0) -- the last position, k - window, is never
+ *      tested (filter.go:202) -- and a record is a HIT when some tested sum >= threshold.  Hits are dropped; with UKM_F_INVERT
+ *      only hits are kept.  k in 1..64 (the hashed flag plays no part: bases above bit 63 read as 0, as Go's `code >>= 2`
+ *      gives); penalties are plain ints, negative ones included; window >= 1, threshold >= 0.
+ *      ukm_sample: keeps record j (1-based) when j >= start and (j - start) % window == 0; start >= 1, window >= 1. */
+int ukm_grep(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint32_t file_taxid, uint64_t n,
+             int canonical_k, const uint64_t *q_keys, const uint32_t *q_taxids, uint64_t nq, uint32_t flags,
+             uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
+int ukm_filter(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n, int k, int window,
+               int penalty_s, int penalty_d, int threshold, uint32_t flags,
+               uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
+int ukm_sample(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n, uint64_t start,
+               uint64_t window, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
 
 /* ---- k-way merge: replaces mergeChunksFile (util-sort.go:227-606).  Streams are expected
  *      to be sorted (chunk files); an unsorted one is tolerated (the call then sorts the

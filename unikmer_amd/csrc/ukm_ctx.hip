@@ -37,7 +37,7 @@ extern char **environ;
 // the option keys a host may set (ukm_ctx_set_option): key "punion" is knob UKM_PUNION, and so on
 static const char *const UKM_OPTION_KEYS[] = {
     "punion", "punion_tax", "punion_ranked", "place", "srmerge", "kway", "no_kway", "no_fold", "no_pfold", "pfold_tax", "common_probe",
-    "sort_local", "sort_counting", "sort_fan", "win_strip", "nthash_strip", "force_ticket", "setop_src", "setop_defer", "punion_clade", "srmerge_clade", "map_sorted",
+    "sort_local", "sort_counting", "sort_fan", "win_strip", "nthash_strip", "force_ticket", "setop_src", "setop_defer", "punion_clade", "srmerge_clade", "map_sorted", "grep_lds",
     // tuning / diagnostics (developer)
     "punion_k0", "punion_claim", "punion_debug", "kway_k", "kway_r", "kway_top2", "kway_debug", "srmerge_fill", "srmerge_spr", "srmerge_buckets",
     "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_fix", "map_dir_slack",
@@ -93,6 +93,7 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     if (!c || !key || !value) UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_get_stat: NULL argument");
     if (strcmp(key, "punion_attempts") == 0) *value = c->stat_punion_attempts;
     else if (strcmp(key, "sort_fused_hist") == 0) *value = c->stat_sort_fused_hist;
+    else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "workspace_bytes") == 0) {
         u64 t = 0;
         for (auto &b : c->blocks) t += b.cap;

@@ -152,6 +152,7 @@ struct ukm_ctx {
     std::map<std::string, std::string> knobs, opts;
     bool env_live = false;
     // statistics a host or a test may ask for (ukm_ctx_get_stat)
+    u64 stat_grep_route = 0;  // membership shape of the last ukm_grep: 1 queries in LDS, 2 sorted queries behind a prefix directory, 3 taxid bitmap, 0 no kernel
     u64 stat_punion_attempts = 0;  // base sets the last probe union / counting probes built (2: the retry with 4 x the files ran)
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device

@@ -5,7 +5,7 @@
 //     windows whose code is in the set and, without -M, occurs once among the windows of its genome).
 //
 // Both are a JOIN of the genome's windows (run_windows, ukm_encode.hip) against a sorted code array, done in genome order:
-//   join_kernel   every window looks its code up through a PREFIX DIRECTORY of the sorted array (dir[p] = lower bound of
+//   join_kernel   every window looks its code up through a PREFIX DIRECTORY of the sorted array (ukm_dir.h; dir[p] = lower bound of
 //                 prefix p, 2^B + 1 words with B = log2(n) - 1: the bucket of a prefix holds 2-4 codes, one 128-byte line
 //                 most of the time) -- one directory read and one or two reads of the array per window instead of the
 //                 ~log2(n) dependent gathers of a whole binary search (every step of a per-lane search in an array
@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ukm_device.h"
+#include "ukm_dir.h"
 #include "ukm_map.h"
 
 namespace {
@@ -41,14 +42,6 @@ constexpr int TILE = NT * VT;
 enum : u64 { MAP_FLAG_TIMEOUT = 4 };  // result word [1]
 enum : u32 { F_GOOD = 1, F_REC = 2 }; // flag byte of a window: good / first window of its record
 
-// first index in [lo, hi) with a[i] >= x
-__device__ __forceinline__ u64 lower_bound_u64(const u64 *a, u64 lo, u64 hi, u64 x) {
-    while (lo < hi) {
-        const u64 mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 // first index in [0, n) with a[i] > x
 __device__ __forceinline__ u64 upper_bound_u64(const u64 *a, u64 n, u64 x) {
     u64 lo = 0, hi = n;
@@ -57,33 +50,6 @@ __device__ __forceinline__ u64 upper_bound_u64(const u64 *a, u64 n, u64 x) {
         if (a[mid] <= x) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-// prefix directory of a sorted array: dir[p] = lower bound of (p << shift), p = 0 .. nb; dir[nb] = n
-struct Dir {
-    const u64 *keys;
-    const u32 *dir;
-    u64 n;
-    int shift;
-    u32 nb;
-};
-
-__global__ void dir_build_kernel(const u64 *keys, u64 n, int shift, u32 nb, u32 *dir) {
-    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > (u64)nb) return;
-    dir[p] = p == (u64)nb ? (u32)n : (u32)lower_bound_u64(keys, 0, n, p << shift);
-}
-
-__device__ __forceinline__ void dir_bucket(const Dir &d, u64 x, u32 &lo, u32 &len) {
-    u64 b = x >> d.shift;
-    if (b >= (u64)d.nb) b = (u64)d.nb - 1;  // (a value wider than the directory's key width: behind everything in the last bucket)
-    lo = d.dir[b];
-    len = d.dir[b + 1] - lo;
-}
-__device__ __forceinline__ u32 dir_lower_bound(const Dir &d, u64 x) {
-    u32 lo, len;
-    dir_bucket(d, x, lo, len);
-    return (u32)lower_bound_u64(d.keys, lo, (u64)lo + len, x);
 }
 
 __global__ void iota_u32_kernel(u32 *v, u64 n) {
@@ -116,34 +82,14 @@ __global__ __launch_bounds__(NT) void join_kernel(JoinArgs p) {
     const u64 tile = COMPACT ? lb_tile_id<TICKET>(p.ticket, &s_misc[0]) : (u64)blockIdx.x;
     const u64 i0 = tile * (u64)TILE + (u64)tid * VT;
     u64 x[VT];
-    u32 lo[VT], len[VT];
-#pragma unroll
-    for (int s = 0; s < VT; s++) x[s] = (i0 + s < p.n) ? p.w[i0 + s] : 0;
+    u32 lo[VT];
+    u32 valid = 0;
 #pragma unroll
     for (int s = 0; s < VT; s++) {
-        lo[s] = 0; len[s] = 0;
-        if (i0 + s < p.n) dir_bucket(p.d, x[s], lo[s], len[s]);
+        x[s] = (i0 + s < p.n) ? p.w[i0 + s] : 0;
+        valid |= (i0 + s < p.n) ? 1u << s : 0u;
     }
-    // the eight searches side by side: every round has eight independent loads in flight (a bucket is a few codes: 2-3
-    // rounds).  The lower bound ends on the last probe that was not below x, so whether it IS x is known without another
-    // read; a search that never saw such a probe ends on the first code of a later prefix, which cannot be x.
-    u32 hit = 0;
-    for (;;) {
-        bool any = false;
-#pragma unroll
-        for (int s = 0; s < VT; s++)
-            if (len[s]) {
-                any = true;
-                const u32 half = len[s] >> 1;
-                const u64 v = p.d.keys[lo[s] + half];
-                if (v < x[s]) { lo[s] += half + 1; len[s] -= half + 1; }
-                else {
-                    len[s] = half;
-                    hit = (hit & ~(1u << s)) | (v == x[s] ? 1u << s : 0u);
-                }
-            }
-        if (!any) break;
-    }
+    const u32 hit = dir_search_n<VT>(p.d, x, valid, lo);  // (ukm_dir.h: the eight searches side by side)
     if (p.flag && i0 < p.n) {
         u64 f8 = 0;
 #pragma unroll
@@ -319,18 +265,8 @@ __global__ void expand_kernel(const u64 *hk, const u32 *hv, u64 n, const u64 *wi
 // ---- host steps -------------------------------------------------------------------------------------------------------
 unsigned blocks_for(u64 n) { return (unsigned)((n + NT - 1) / NT); }
 
-int build_dir(ukm_ctx *c, const u64 *keys, u64 n, int key_bits, Dir *d) {
-    int lg = 0;
-    while (lg < 63 && (2ull << lg) <= n) lg++;  // floor(log2(n))
-    const int slack = std::max(0, std::min(8, ukm_env_int(c, "UKM_MAP_DIR_SLACK", 1)));  // log2 of the codes per prefix (developer knob; 1 / 2 / 3 measured: DESIGN.md 4.14)
-    const int B = std::max(1, std::min(std::min(lg - slack, 24), key_bits));
-    u32 *dir = nullptr;
-    UKM_TRY(ws_alloc_t(c, ((size_t)1 << B) + 1, &dir));
-    d->keys = keys; d->dir = dir; d->n = n; d->shift = key_bits - B; d->nb = 1u << B;
-    hipLaunchKernelGGL(dir_build_kernel, dim3(blocks_for((u64)d->nb + 1)), dim3(NT), 0, c->stream, keys, n, d->shift, d->nb, dir);
-    UKM_HIP(hipGetLastError());
-    return UKM_OK;
-}
+// log2 of the codes per prefix of the directory (developer knob; 1 / 2 / 3 measured: DESIGN.md 4.14)
+int dir_slack(const ukm_ctx *c) { return ukm_env_int(c, "UKM_MAP_DIR_SLACK", DIR_SLACK_DEFAULT); }
 
 // flag: n rounded up to whole tiles (the kernels read and write 8-byte words)
 size_t flag_bytes(u64 n) { return (size_t)((n + TILE - 1) / TILE * TILE + 8); }
@@ -455,7 +391,7 @@ extern "C" int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *re
         hipLaunchKernelGGL(iota_u32_kernel, dim3(std::min(blocks_for(nq), (unsigned)ctx->num_cu * 16u)), dim3(NT), 0, ctx->stream, qi, nq);
         UKM_TRY(ukm_dev_sort(ctx, qs, qi, nq, 64));
         Dir d;
-        UKM_TRY(build_dir(ctx, qs, nq, hashed ? 64 : 2 * k, &d));
+        UKM_TRY(build_dir(ctx, qs, nq, hashed ? 64 : 2 * k, dir_slack(ctx), &d));
         // hits in window order.  The caller's capacity bounds the first attempt's buffers (a host that asks for a few
         // positions pays for a few); more hits than that: the exact number goes back with UKM_ERR_CAPACITY
         const u64 hcap = std::min<u64>(W.n, out_cap);
@@ -536,7 +472,7 @@ extern "C" int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_o
         if (W.n == 0 || n_set == 0) return UKM_OK;
         const int key_bits = hashed ? 64 : 2 * k;
         Dir d;
-        UKM_TRY(build_dir(ctx, set, n_set, key_bits, &d));
+        UKM_TRY(build_dir(ctx, set, n_set, key_bits, dir_slack(ctx), &d));
         u8 *flag = nullptr;
         UKM_TRY(ws_alloc_t(ctx, flag_bytes(W.n), &flag));
         Genomes G = {nullptr, n_genome};

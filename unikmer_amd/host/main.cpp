@@ -10,10 +10,12 @@
 //   union / inter / diff / common / merge -> ukm_union / ukm_inter / ukm_diff / ukm_common / ukm_merge_k
 //   locate (locate.go)  genome FASTA + .unik codes -> ukm_locate -> BED6
 //   map / uniqs (map.go, -x 0 -X 0, linear)  .unik files -> ukm_union -> per genome file ukm_map -> BED3 | FASTA
+//   grep / filter / sample (grep.go, filter.go, sample.go)  per input file ukm_grep | ukm_filter | ukm_sample: the kept records
+//          in input order with their own taxids; grep -s/-u/-d -> ukm_sort_* -> ukm_unique
 // CPU-only commands (no GPU needed): view, dump, num, info/stats, concat, head, encode, decode.
 // `count` keeps the window values on the device from encode to the final set (chunked, double-buffered upload).
-// Not implemented (SURVEY.md §2a out of scope): grep, filter, rfilter, tsplit, sample, map -x/-X/--circular,
-// autocompletion; count -S (syncmer sketch: third-party rule not reconstructable from the tree).
+// Not implemented (SURVEY.md §2a out of scope): rfilter (needs rank names), tsplit (a sort by taxid), grep -m/-O/-S/--force,
+// map -x/-X/--circular, autocompletion; count -S (syncmer sketch: third-party rule not reconstructable from the tree).
 #include <dirent.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -1312,6 +1314,277 @@ static int cmd_map(int argc, char **argv) {  // map.go:57-491 at -x 0 -X 0, line
 }
 
 // =================================================================================================
+// record selection: grep / filter / sample (ukm_grep / ukm_filter / ukm_sample keep input order and every record's own taxid)
+// =================================================================================================
+// an output that follows an input header (filter.go:123-125, sample.go:116-122): no global taxid, the reader's taxid width
+static void write_following(const string &out_file, const Options &o, const unik::Header &h0, u32 mode, const u64 *codes, const u32 *taxids, u64 n) {
+    unik::OutStream os(out_file, o.compress, o.level);
+    unik::Writer w(os, h0.k, mode & ~(u32)unik::UnikScaled);
+    w.h.taxid_bytes = h0.taxid_bytes;
+    if (mode & unik::UnikScaled) w.set_scale(h0.scale, h0.max_hash);
+    w.set_number(n);
+    const bool tx = (mode & unik::UnikIncludeTaxID) != 0;
+    for (u64 i = 0; i < n; i++) {
+        if (tx) w.write_code_with_taxid(codes[i], taxids[i]);
+        else w.write_code(codes[i]);
+    }
+    w.flush();
+    os.close();
+    info("%llu k-mers saved to %s", (unsigned long long)n, out_file.c_str());
+}
+// the taxids of a file's selected records: its own column, or the file's one taxid for every record
+static void append_selected(const Loaded &L, bool tax, const vector<u64> &ok, const vector<u32> &ot, u64 n, vector<u64> &codes, vector<u32> &taxids) {
+    codes.insert(codes.end(), ok.begin(), ok.begin() + (long)n);
+    if (!tax) return;
+    if (L.per_record()) taxids.insert(taxids.end(), ot.begin(), ot.begin() + (long)n);
+    else taxids.insert(taxids.end(), (size_t)n, L.file_taxid);
+}
+
+static int cmd_sample(int argc, char **argv) {  // sample.go:45-166
+    Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'s', "start", true}, {'w', "window", true}});
+    Options o = get_options(a);
+    vector<string> files = get_files(a, o);
+    const long long start = a.num("start", 1), window = a.num("window", 1);
+    if (start <= 0) die("value of flag --start should be greater than 0");
+    if (window <= 0) die("value of flag --window should be greater than 0");
+    const string out_file = out_name(a.str("out-prefix", "-"));
+    // The header follows the first input (sample.go:116-120) and every record is written with the taxid the reader hands
+    // out (:136,147), also under -I: -I only switches off the include-taxid flag for files with ONE taxid and the check that
+    // all inputs agree (:114,125).  So the taxid columns are always loaded.
+    Options oo = o;
+    oo.ignore_taxid = false;
+    Inputs in = load_inputs(files, oo, false, false, o.ignore_taxid);
+    u32 mode = in.h0.flag;
+    if (!o.ignore_taxid && in.has_taxid) mode |= unik::UnikIncludeTaxID;  // "for multiple input files"
+    const bool tax = (mode & unik::UnikIncludeTaxID) != 0;
+    vector<u64> codes;
+    vector<u32> taxids;
+    if (in.total) {
+        Gpu g(o.gpu);
+        vector<u64> ok;
+        vector<u32> ot;
+        for (auto &L : in.files) {  // j restarts for every file (sample.go:134)
+            if (L.codes.empty()) continue;
+            ok.resize(L.codes.size());
+            const bool own = tax && L.per_record();
+            if (own) ot.resize(L.codes.size());
+            u64 n = 0;
+            ck(ukm_sample(g.c, L.codes.data(), own ? L.taxids.data() : nullptr, L.codes.size(), (u64)start, (u64)window,
+                          ok.data(), own ? ot.data() : nullptr, ok.size(), &n));
+            append_selected(L, tax, ok, ot, n, codes, taxids);
+        }
+    }
+    write_following(out_file, o, in.h0, mode, codes.data(), taxids.data(), codes.size());
+    return 0;
+}
+
+static int cmd_filter(int argc, char **argv) {  // filter.go:43-168
+    Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'v', "invert", false}, {'t', "threshold", true}, {'w', "window", true},
+                                     {'s', "penalty-s", true}, {'d', "penalty-d", true}});
+    Options o = get_options(a);
+    vector<string> files = get_files(a, o);
+    if (files.size() > 1) die("no more than one file should be given");
+    const long long threshold = a.num("threshold", 15);
+    if (threshold < 0) die("value of flag --threshold should be greater than or equal to 0");
+    long long window = a.num("window", 7);
+    if (window <= 0) die("value of flag --window should be greater than 0");
+    const int ps = (int)a.num("penalty-s", 3), pd = (int)a.num("penalty-d", 1);
+    const string out_file = out_name(a.str("out-prefix", "-"));
+    Options oo = o;
+    oo.ignore_taxid = false;  // the header follows the input (filter.go:123): records keep their taxids
+    Loaded L = load_unik(files[0], oo);
+    const int k = L.h.k;
+    if (window > k) {
+        warn("window size (%lld) is bigger than k (%d)", window, k);
+        window = k;
+    }
+    const bool tax = L.per_record();
+    vector<u64> ok(std::max<size_t>(L.codes.size(), 1));
+    vector<u32> ot(tax ? ok.size() : 0);
+    u64 n = 0;
+    if (!L.codes.empty()) {
+        Gpu g(o.gpu);
+        ck(ukm_filter(g.c, L.codes.data(), tax ? L.taxids.data() : nullptr, L.codes.size(), k, (int)window, ps, pd, (int)threshold,
+                      a.has("invert") ? UKM_F_INVERT : 0, ok.data(), tax ? ot.data() : nullptr, ok.size(), &n));
+    }
+    write_following(out_file, o, L.h, L.h.flag, ok.data(), ot.data(), n);
+    return 0;
+}
+
+static void hash_kmers_on_device(Gpu &g, const vector<string> &kmers, int k, bool canonical, vector<u64> &out);
+
+// util.go:173-245 extendDegenerateSeq: every sequence a degenerate one stands for, in the reference's order
+static vector<string> extend_degenerate(const string &q) {
+    static const std::map<char, string> M = {
+        {'A', "A"}, {'T', "T"}, {'U', "U"}, {'C', "C"}, {'G', "G"}, {'R', "AG"}, {'Y', "CT"}, {'M', "AC"}, {'K', "GT"}, {'S', "CG"}, {'W', "AT"},
+        {'H', "ACT"}, {'B', "CGT"}, {'V', "ACG"}, {'D', "AGT"}, {'N', "ACGT"}, {'a', "a"}, {'t', "t"}, {'u', "u"}, {'c', "c"}, {'g', "g"},
+        {'r', "ag"}, {'y', "ct"}, {'m', "ac"}, {'k', "gt"}, {'s', "cg"}, {'w', "at"}, {'h', "act"}, {'b', "cgt"}, {'v', "acg"}, {'d', "agt"},
+        {'n', "acgt"}};
+    vector<string> seqs = {""};
+    for (char base : q) {
+        auto it = M.find(base);
+        if (it == M.end()) die("fail to extend degenerate sequence '%s': invalid degenerate bases: %c", q.c_str(), base);
+        const string &db = it->second;
+        vector<string> more;
+        for (size_t i = 1; i < db.size(); i++)
+            for (auto &sq : seqs) more.push_back(sq + db[i]);
+        for (auto &sq : seqs) sq += db[0];
+        seqs.insert(seqs.end(), more.begin(), more.end());
+    }
+    return seqs;
+}
+
+static int cmd_grep(int argc, char **argv) {  // grep.go:62-890
+    Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'q', "query", true}, {'f', "query-file", true}, {'F', "query-unik-file", true},
+                                     {'t', "query-is-taxid", false}, {'D', "degenerate", false}, {'v', "invert-match", false}, {'s', "sort", false},
+                                     {'u', "unique", false}, {'d', "repeated", false}, {'m', "multiple-outfiles", false}, {'O', "out-dir", true},
+                                     {'S', "out-suffix", true}, {0, "force", false}});
+    Options o = get_options(a);
+    vector<string> files = get_files(a, o);
+    const vector<string> queries = a.list("query"), query_files = a.list("query-file"), query_unik_files = a.list("query-unik-file");
+    const bool by_taxid = a.has("query-is-taxid"), invert = a.has("invert-match"), degenerate = a.has("degenerate");
+    const bool uniq = a.has("unique"), rep = a.has("repeated");
+    bool sort_kmers = a.has("sort");
+    if ((uniq || rep) && !sort_kmers) {
+        info("flag -s/--sort is switched on when given -u/--unique or -d/--repeated");
+        sort_kmers = true;
+    }
+    if (queries.empty() && query_files.empty() && query_unik_files.empty())
+        die("one of flags -q/--query, -f/--query-file and -F/--query-unik-file needed");
+    if (a.has("multiple-outfiles") || a.has("out-dir") || a.has("out-suffix") || a.has("force"))
+        die("flag -m/--multiple-outfiles (and -O/--out-dir, -S/--out-suffix, --force) is not supported in this build: run grep once per input file");
+    int k = -1;
+    // text queries from -q and -f (grep.go:122-166)
+    vector<string> query_list;
+    auto add_query = [&](const string &q) {
+        if (!by_taxid) {
+            if (k == -1) k = (int)q.size();
+            else if ((int)q.size() != k) die("length of query sequence are inconsistent: (%zu) != (%d): %s", q.size(), k, q.c_str());
+        }
+        query_list.push_back(q);
+    };
+    for (auto &q : queries) if (!q.empty()) add_query(q);
+    for (auto &qf : query_files) {
+        info("loading queries from k-mer file: %s", qf.c_str());
+        unik::InStream in(qf);
+        string text, chunk(1 << 20, '\0');
+        for (;;) { size_t got = in.read(&chunk[0], chunk.size()); if (!got) break; text.append(chunk.data(), got); }
+        std::istringstream ss(text);
+        string line;
+        while (std::getline(ss, line)) {
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+            if (!line.empty()) add_query(line);
+        }
+    }
+    vector<u64> q_codes;
+    vector<u32> q_taxids;
+    vector<string> q_text;  // k-mer text, encoded once the inputs say how (every query is searched: grep.go:173-190 keeps the last one only)
+    for (auto &q : query_list) {
+        if (by_taxid) {
+            char *e = nullptr;
+            errno = 0;
+            const unsigned long long v = strtoull(q.c_str(), &e, 10);
+            if (e == q.c_str() || *e || errno || v < 1 || v > 0xFFFFFFFFull || q[0] == '-')
+                die("query taxid should be positive integer in range of [1, %u]: %s", 0xFFFFFFFFu, q.c_str());
+            q_taxids.push_back((u32)v);
+        } else if (degenerate) {
+            for (auto &sq : extend_degenerate(q)) q_text.push_back(sq);
+        } else {
+            q_text.push_back(q);
+        }
+    }
+    // queries from .unik files (grep.go:207-270)
+    unik::Header qh0;
+    bool have_qh0 = false;
+    for (auto &qf : query_unik_files) {
+        info("loading queries from .unik file: %s", qf.c_str());
+        Options oo = o;
+        oo.ignore_taxid = false;
+        Loaded Q = load_unik(qf, oo);
+        if (by_taxid && !Q.h.has_taxid_info()) die("no taxids found in file: %s", qf.c_str());
+        if (!have_qh0) {
+            if (k != -1) {
+                if (k != Q.h.k) die("k-mer length not consistent (%d != %d), please check with \"unikmer stats\": %s", k, Q.h.k, qf.c_str());
+            } else k = Q.h.k;
+            qh0 = Q.h;
+            have_qh0 = true;
+        } else check_compat(qh0, Q.h, qf);
+        if (by_taxid) {
+            if (Q.per_record()) q_taxids.insert(q_taxids.end(), Q.taxids.begin(), Q.taxids.end());
+            else if (!Q.codes.empty()) q_taxids.push_back(Q.file_taxid);
+            continue;
+        }
+        const bool make_canonical = !Q.h.is_canonical() && !Q.h.is_hashed();
+        for (u64 c : Q.codes) q_codes.push_back(make_canonical ? std::min(c, revcomp(c, Q.h.k)) : c);
+    }
+    // the inputs: compatible with the query files and with each other, same taxid situation (grep.go:439-441,550-563)
+    Inputs in = load_inputs(files, o, false, false, false);
+    if (have_qh0) check_compat(qh0, in.h0, files[0]);
+    if (!by_taxid && k != in.k) die("K (%d) of binary file '%s' not equal to query K (%d)", in.k, files[0].c_str(), k);
+    const bool tax = in.has_taxid;
+    if ((uniq || rep) && tax)
+        die("flag -u/--unique and -d/--repeated are not supported for inputs with taxids in this build (which duplicate's taxid the "
+            "reference keeps is not defined); add -I/--ignore-taxid");
+    if (by_taxid && !in.files.empty() && !in.h0.has_taxid_info()) info("the inputs carry no taxids: every record has taxid 0");
+    if (!by_taxid && !in.hashed)
+        for (auto &q : q_text) {
+            u64 c;
+            if (!encode_kmer(q, c)) die("fail to encode query '%s'", q.c_str());
+            q_codes.push_back(std::min(c, revcomp(c, (int)q.size())));
+        }
+    const string out_file = out_name(a.str("out-prefix", "-"));
+    u32 mode = unik::UnikCanonical;  // "forcing using canonical" (grep.go:499)
+    if (sort_kmers) mode |= unik::UnikSorted;
+    else if (files.size() == 1 && in.h0.is_sorted()) mode |= unik::UnikSorted;
+    else if (o.compact && !in.hashed) mode |= unik::UnikCompact;
+    if (tax) mode |= unik::UnikIncludeTaxID;
+    if (in.hashed) mode |= unik::UnikHashed;
+
+    vector<u64> codes;
+    vector<u32> taxids;
+    if (in.total) {
+        Gpu g(o.gpu);
+        if (!by_taxid && in.hashed && !q_text.empty()) {  // ntHash with the FILE's canonical flag, one window per query (grep.go:452-460)
+            vector<u64> hv;
+            hash_kmers_on_device(g, q_text, k, in.canonical, hv);
+            q_codes.insert(q_codes.end(), hv.begin(), hv.end());
+        }
+        if (by_taxid) info("%zu taxids loaded", q_taxids.size());
+        else info("%zu k-mers loaded", q_codes.size());
+        const int canonical_k = (!in.canonical && !in.hashed) ? in.k : 0;
+        const u64 nq = by_taxid ? q_taxids.size() : q_codes.size();
+        vector<u64> ok;
+        vector<u32> ot;
+        for (auto &L : in.files) {  // records of several inputs in FILE order
+            if (L.codes.empty()) continue;
+            ok.resize(L.codes.size());
+            const bool own = tax && L.per_record();
+            if (own) ot.resize(L.codes.size());
+            u64 n = 0;
+            ck(ukm_grep(g.c, L.codes.data(), own ? L.taxids.data() : nullptr, tax ? L.file_taxid : 0u, L.codes.size(), canonical_k,
+                        by_taxid ? nullptr : q_codes.data(), by_taxid ? q_taxids.data() : nullptr, nq,
+                        (invert ? UKM_F_INVERT : 0u) | (by_taxid ? UKM_F_QUERY_TAXID : 0u), ok.data(), own ? ot.data() : nullptr, ok.size(), &n));
+            append_selected(L, tax, ok, ot, n, codes, taxids);
+        }
+        if (sort_kmers && !codes.empty()) {  // grep.go:790-875
+            const int key_bits = in.hashed ? 64 : 2 * in.k;
+            info("sorting %zu k-mers", codes.size());
+            if (tax) ck(ukm_sort_pairs(g.c, codes.data(), taxids.data(), codes.size(), key_bits));
+            else ck(ukm_sort_u64(g.c, codes.data(), codes.size(), key_bits));
+            if (uniq || rep) {  // (never with taxids: refused above)
+                vector<u64> u(codes.size());
+                u64 n = 0;
+                ck(ukm_unique(g.c, codes.data(), nullptr, codes.size(), uniq ? UKM_UNIQUE : UKM_REPEATED, u.data(), nullptr, u.size(), &n));
+                u.resize(n);
+                codes.swap(u);
+            }
+        }
+    }
+    write_following(out_file, o, in.h0, mode, codes.data(), taxids.data(), codes.size());
+    return 0;
+}
+
+// =================================================================================================
 // CPU-only commands
 // =================================================================================================
 static int cmd_view(int argc, char **argv) {  // view.go:163-218
@@ -1711,7 +1984,7 @@ static void usage() {
     fprintf(stderr,
             "unikmer (HIP) - k-mer set operations on AMD MI355X behind the unikmer command line\n\n"
             "Usage: unikmer <command> [flags] [files]\n\n"
-            "GPU commands : count sort split merge union inter diff common locate map(uniqs)\n"
+            "GPU commands : count sort split merge union inter diff common locate map(uniqs) grep filter sample\n"
             "CPU commands : view dump num info(stats) concat head encode decode version\n"
             "Global flags : -j --verbose -C --compression-level -c -i -I --max-taxid --data-dir --gpu\n");
 }
@@ -1731,6 +2004,9 @@ int main(int argc, char **argv) {
         if (cmd == "split") return cmd_setop(C_SPLIT, argc, argv);
         if (cmd == "locate") return cmd_locate(argc, argv);
         if (cmd == "map" || cmd == "uniqs") return cmd_map(argc, argv);
+        if (cmd == "grep") return cmd_grep(argc, argv);
+        if (cmd == "filter") return cmd_filter(argc, argv);
+        if (cmd == "sample") return cmd_sample(argc, argv);
         if (cmd == "view") return cmd_view(argc, argv);
         if (cmd == "dump") return cmd_dump(argc, argv);
         if (cmd == "num") return cmd_num(argc, argv);

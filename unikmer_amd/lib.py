@@ -19,6 +19,7 @@ ERR_UNSORTED, ERR_NO_TAXONOMY, ERR_CAPACITY, ERR_K, ERR_PEER = -5, -6, -7, -8, -
 PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 F_MIX_TAXID, F_CMP_TAXID = 2, 4
+F_INVERT, F_QUERY_TAXID = 8, 16   # grep -v / filter -v; grep -t
 F_DEVICE_STREAMS = 256   # every stream pointer of an n-way call is a device pointer (no per-pointer driver query)
 # Context.last_route(): which internal route answered the last n-way call (include/unikmer_hip.h: UKM_ROUTE_*)
 ROUTE_NONE, ROUTE_TREE, ROUTE_KWAY, ROUTE_PUNION, ROUTE_SRMERGE, ROUTE_SRCOMMON, ROUTE_PCOMMON, ROUTE_PLACE = range(8)
@@ -36,7 +37,7 @@ SYMBOLS = [
     "ukm_shard_splitters", "ukm_shard_splitters_plan", "ukm_shard_counts_tax", "ukm_shard_counts_plan", "ukm_count",
     "ukm_ctx_set_option", "ukm_ctx_unset_option", "ukm_ctx_get_option", "ukm_ctx_get_stat",
     "ukm_setop2_ft", "ukm_union_ft", "ukm_inter_ft", "ukm_diff_ft", "ukm_common_ft", "ukm_merge_k_ft",
-    "ukm_locate", "ukm_map",
+    "ukm_locate", "ukm_map", "ukm_grep", "ukm_filter", "ukm_sample",
 ]
 
 
@@ -126,6 +127,9 @@ def load():
     L.ukm_count.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, u64, i32, vp, u64, pu64]
     L.ukm_locate.argtypes = [vp, vp, vp, u64, i32, i32, i32, vp, u64, vp, vp, vp, u64, pu64]
     L.ukm_map.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, vp, u64, i32, u64, vp, vp, vp, u64, pu64]
+    L.ukm_grep.argtypes = [vp, vp, vp, u32, u64, i32, vp, vp, u64, u32, vp, vp, u64, pu64]
+    L.ukm_filter.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, i32, u32, vp, vp, u64, pu64]
+    L.ukm_sample.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, u64, pu64]
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -416,6 +420,53 @@ class Context:
         return self._coords(lambda o, cap, n: self.L.ukm_map(self.h, pb, poff, noff - 1, pg, ng - 1, int(k), int(hashed), ps, ns,
                                                              int(allow_multi), int(min_len), o[0], o[1], o[2], cap, C.byref(n)),
                             bases, (np.uint32, np.uint64, np.uint64), out_cap)
+
+    # ---- record selection (grep / filter / sample): kept records in input order, taxids copied ----
+    def _select(self, call, keys, taxids, bound, out, out_taxids):
+        """taxids: an array (one per record), an int (the file's ONE taxid: only grep by taxid looks at it) or None"""
+        pk, n, k1 = _ptr(keys, np.uint64)
+        per_record = taxids is not None and not _is_file_taxid(taxids)
+        pt, nt, k2 = _ptr(taxids if per_record else None, np.uint32)
+        if per_record:
+            assert nt == n
+        cap = n if bound is None else bound(n)
+        if out is None:
+            out = _empty_like_kind(keys, cap, np.uint64)
+        if per_record and out_taxids is None:
+            out_taxids = _empty_like_kind(keys, cap, np.uint32)
+        po, cap, _ = _ptr(out, np.uint64)
+        pot, _, _ = _ptr(out_taxids if per_record else None, np.uint32)
+        m = C.c_uint64()
+        _check(call(pk, pt, n, po, pot, cap, C.byref(m)))
+        return (out[: m.value], out_taxids[: m.value]) if per_record else out[: m.value]
+
+    def grep(self, keys, queries=None, query_taxids=None, taxids=None, canonical_k=0, invert=False, out=None, out_taxids=None):
+        """`unikmer grep` (grep.go:617-676): the records whose code is among `queries` -- or whose taxid is among
+        `query_taxids` -- in input order, duplicates kept, each with its own taxid.  canonical_k in 1..32: every code is made
+        canonical first (files that are neither canonical nor hashed).  taxids as an int: the file's one taxid."""
+        if (queries is None) == (query_taxids is None):
+            raise ValueError("grep: give exactly one of queries and query_taxids")
+        pq, nq, k3 = _ptr(queries, np.uint64)
+        pqt, nqt, k4 = _ptr(query_taxids, np.uint32)
+        flags = (F_INVERT if invert else 0) | (F_QUERY_TAXID if query_taxids is not None else 0)
+        ft = int(taxids) if _is_file_taxid(taxids) else 0
+        return self._select(lambda pk, pt, n, po, pot, cap, m: self.L.ukm_grep(self.h, pk, pt, ft, n, int(canonical_k), pq, pqt,
+                                                                               nq if queries is not None else nqt, flags, po, pot, cap, m),
+                            keys, taxids, None, out, out_taxids)
+
+    def filter(self, keys, k, taxids=None, threshold=15, window=7, penalty_s=3, penalty_d=1, invert=False, out=None, out_taxids=None):
+        """`unikmer filter` (filter.go:181-221): drops the low-complexity k-mers (invert: keeps only them)"""
+        return self._select(lambda pk, pt, n, po, pot, cap, m: self.L.ukm_filter(self.h, pk, pt, n, int(k), int(window), int(penalty_s),
+                                                                                 int(penalty_d), int(threshold), F_INVERT if invert else 0,
+                                                                                 po, pot, cap, m),
+                            keys, taxids, None, out, out_taxids)
+
+    def sample(self, keys, start=1, window=1, taxids=None, out=None, out_taxids=None):
+        """`unikmer sample` (sample.go:134-148): record j (1-based) when j >= start and (j - start) % window == 0"""
+        start, window = int(start), int(window)
+        return self._select(lambda pk, pt, n, po, pot, cap, m: self.L.ukm_sample(self.h, pk, pt, n, start, window, po, pot, cap, m),
+                            keys, taxids, (lambda n: (n - start) // window + 1 if start >= 1 and window >= 1 and n >= start else 0),
+                            out, out_taxids)
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
