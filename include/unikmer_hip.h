@@ -19,6 +19,9 @@
  *  - Outputs are caller-allocated with capacity `out_cap` (elements); upper bounds:
  *    union <= sum(n), inter <= n[0], diff <= n[0], common <= sum(n), unique <= n (2n for
  *    UKM_REPEATED_CHUNK), encode/nthash <= number of windows.  Too small -> UKM_ERR_CAPACITY.
+ *    Size query: with out_cap == 0 every output pointer may be NULL (out_taxids too, also for records that carry taxids); the
+ *    call returns UKM_ERR_CAPACITY with the size needed in *n_out, or UKM_OK with *n_out == 0 for an empty result.  A failed
+ *    call leaves [0, out_cap) unspecified; nothing outside [0, out_cap) is ever written.
  *  - A ukm_ctx owns one HIP stream and one growable device workspace; it is NOT thread-safe.
  *    Use one ctx per calling OS thread (the reference calls these seams from several
  *    goroutines: sort.go:257, diff.go:280).  There is no global mutable state.

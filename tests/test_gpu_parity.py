@@ -99,8 +99,9 @@ def test_setop2_unsorted_is_an_error(ctx, L):
 def test_setop2_capacity_error(ctx, L):
     A, B = synth_sets(10000, 20)
     out = np.empty(10, dtype=np.uint64)
-    with pytest.raises(L.CapacityError):
+    with pytest.raises(L.CapacityError) as e:
         ctx.setop2(L.OP_UNION, A, B, out=out)
+    assert e.value.needed == len(np.union1d(A, B))     # *n_out holds the size that is needed
 
 
 def test_setop2_multiset_semantics(ctx, O, L):

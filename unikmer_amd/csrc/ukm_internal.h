@@ -230,6 +230,14 @@ static inline int ukm_out_t(ukm_ctx *c, T *p, size_t n, T **dev) {
     *dev = (T *)d;
     return rc;
 }
+// Output array of an entry point that answers a size query (include/unikmer_hip.h: with out_cap == 0 every output pointer
+// may be NULL): the routes get one workspace word in place of a NULL array -- nothing is copied back -- so none of them
+// ever holds a null output pointer, whatever it does about the capacity.
+template <typename T>
+static inline int ukm_out_query_t(ukm_ctx *c, T *p, size_t n, T **dev) {
+    if (p != nullptr || n != 0) return ukm_out_t(c, p, n, dev);
+    return ws_alloc_t(c, 1, dev);
+}
 void ukm_out_resize(ukm_ctx *c, void *host, size_t bytes);
 // In-place staging (sort): host array copied in, and copied back at finish.
 int ukm_inout(ukm_ctx *c, void *p, size_t bytes, void **dev);

@@ -213,9 +213,10 @@ int run_entry(ukm_ctx *ctx, uint64_t *out_keys, uint32_t *out_taxids, uint64_t o
     UKM_TRY(ukm_begin(ctx, &s));
     int rc = [&]() -> int {
         OutBufs o;
-        UKM_TRY(ukm_out_t(ctx, out_keys, out_cap, &o.k));
-        if (tax && !out_taxids) UKM_FAIL(UKM_ERR_INVALID, "records carry taxids but out_taxids is NULL");
-        if (tax) UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &o.t));
+        // (a size query, out_cap == 0, may leave both arrays NULL)
+        UKM_TRY(ukm_out_query_t(ctx, out_keys, out_cap, &o.k));
+        if (tax && !out_taxids && out_cap) UKM_FAIL(UKM_ERR_INVALID, "records carry taxids but out_taxids is NULL");
+        if (tax) UKM_TRY(ukm_out_query_t(ctx, out_taxids, out_cap, &o.t));
         *n_out = 0;
         ctx->last_route = UKM_ROUTE_NONE;
         int r = body(o);

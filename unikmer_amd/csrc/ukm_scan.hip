@@ -509,8 +509,10 @@ extern "C" int ukm_unique(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *ta
         u32 *tout = nullptr;
         UKM_TRY(ukm_in_t(ctx, keys, n, &k));
         UKM_TRY(ukm_in_t(ctx, taxids, n, &t));
-        UKM_TRY(ukm_out_t(ctx, out_keys, out_cap, &out));
-        UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &tout));
+        // (a size query, out_cap == 0, may leave both arrays NULL; without taxids out_taxids stays optional)
+        UKM_TRY(ukm_out_query_t(ctx, out_keys, out_cap, &out));
+        if (taxids) UKM_TRY(ukm_out_query_t(ctx, out_taxids, out_cap, &tout));
+        else UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &tout));
         int r = ukm_dev_unique(ctx, k, t, n, mode, out, tout, out_cap, n_out);
         u64 m = (r == UKM_OK) ? *n_out : 0;
         ukm_out_resize(ctx, out_keys, m * sizeof(u64));

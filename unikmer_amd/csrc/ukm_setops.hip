@@ -1546,7 +1546,9 @@ int ukm_dev_setop2_ct(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u32 cta, 
                 UKM_TRY(run_setop_pass(c, op, a, ta, ra, na, b, tb, rb, nb, tax, flags, tk, tt, na, res, cta, ctb));
                 if (!(res[1] & FLAG_UNSORTED)) {
                     u64 nu = 0;
-                    UKM_TRY(ukm_dev_unique(c, tk, tax ? tt : nullptr, res[0], 5 /*UNIQUE_LAST*/, out, tout, out_cap, &nu));
+                    const int ru = ukm_dev_unique(c, tk, tax ? tt : nullptr, res[0], 5 /*UNIQUE_LAST*/, out, tout, out_cap, &nu);
+                    if (ru == UKM_ERR_CAPACITY) *n_out = nu;  // (the size needed leaves with the error, as below)
+                    UKM_TRY(ru);
                     res[0] = nu;
                 }
             } else {
@@ -1585,8 +1587,11 @@ extern "C" int ukm_setop2_ft(ukm_ctx *ctx, int op, const uint64_t *a_keys, const
         UKM_TRY(ukm_in_t(ctx, b_keys, nb, &b));
         UKM_TRY(ukm_in_t(ctx, a_taxids, na, &ta));
         UKM_TRY(ukm_in_t(ctx, b_taxids, nb, &tb));
-        UKM_TRY(ukm_out_t(ctx, out_keys, out_cap, &out));
-        UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &tout));
+        // (a size query, out_cap == 0, may leave both arrays NULL; without taxids out_taxids stays optional)
+        const bool tax_in = a_taxids || b_taxids || a_file_taxid || b_file_taxid;
+        UKM_TRY(ukm_out_query_t(ctx, out_keys, out_cap, &out));
+        if (tax_in) UKM_TRY(ukm_out_query_t(ctx, out_taxids, out_cap, &tout));
+        else UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &tout));
         // (an empty stream's per-record pointer may be null: its file taxid plays no part then)
         const u32 cta = ta ? 0u : a_file_taxid, ctb = tb ? 0u : b_file_taxid;
         int r = ukm_dev_setop2_ct(ctx, op, a, ta, cta, na, b, tb, ctb, nb, flags & (UKM_F_MIX_TAXID | UKM_F_CMP_TAXID), out, tout, out_cap, n_out);

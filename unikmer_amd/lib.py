@@ -56,7 +56,11 @@ class UnsortedError(UkmError):
 
 
 class CapacityError(UkmError):
-    pass
+    """out_cap was too small; `needed` is the size the library reported in *n_out (None where a call reports none)"""
+
+    def __init__(self, code, msg, needed=None):
+        super().__init__(code, msg)
+        self.needed = needed
 
 
 _lib = None
@@ -177,12 +181,14 @@ class StreamTable:
         self.ref = ref
 
 
-def _check(rc):
+def _check(rc, needed=None):
+    """needed: the call's n_out (UKM_ERR_CAPACITY leaves the required size there: the two-call idiom)"""
     if rc == OK:
         return
     msg = load().ukm_last_error().decode(errors="replace")
-    cls = {ERR_ILLEGAL_BASE: IllegalBaseError, ERR_UNSORTED: UnsortedError,
-           ERR_CAPACITY: CapacityError}.get(rc, UkmError)
+    if rc == ERR_CAPACITY:
+        raise CapacityError(rc, msg, None if needed is None else int(needed))
+    cls = {ERR_ILLEGAL_BASE: IllegalBaseError, ERR_UNSORTED: UnsortedError}.get(rc, UkmError)
     raise cls(rc, msg)
 
 
@@ -338,7 +344,7 @@ class Context:
         else:
             rc = self.L.ukm_nthash(self.h, pb, poff, n_rec, k, int(canonical), int(circular), max_hash, po, cap,
                                    C.byref(n))
-        _check(rc)
+        _check(rc, n.value)
         return out[: n.value]
 
     def encode_kmers(self, bases, rec_off, k, canonical=True, circular=False, out=None):
@@ -347,19 +353,26 @@ class Context:
     def nthash(self, bases, rec_off, k, canonical=True, circular=False, max_hash=0, out=None):
         return self._windows("nt", bases, rec_off, k, canonical, circular, max_hash, out)
 
-    def minimizer(self, bases, rec_off, k, w, circular=False, max_hash=0, with_pos=False):
+    def minimizer(self, bases, rec_off, k, w, circular=False, max_hash=0, with_pos=False, out=None, out_pos=None):
         """Minimizer sketch of every record (sketches.NewMinimizerSketch, count.go:316).  Returns the
-        emitted canonical ntHash values in record/group order (and their window indices)."""
+        emitted canonical ntHash values in record/group order (and their window indices).  out / out_pos: the caller's
+        arrays (out_pos as long as out; giving it implies with_pos)."""
         pb, nb, _ = _ptr(bases, np.uint8)
         poff, noff, _ = _ptr(rec_off, np.uint64)
-        cap = nb
-        out = _empty_like_kind(bases, cap, np.uint64)
-        pos = _empty_like_kind(bases, cap, np.uint64) if with_pos else None
-        po, _, _ = _ptr(out, np.uint64)
-        pp = _ptr(pos, np.uint64)[0] if with_pos else None
+        with_pos = with_pos or out_pos is not None
+        if out is None:
+            cap = nb
+            out = _empty_like_kind(bases, cap, np.uint64)
+            po = _ptr(out, np.uint64)[0]
+        else:
+            po, cap, _ = _ptr(out, np.uint64)
+        pos = out_pos if out_pos is not None else (_empty_like_kind(bases, cap, np.uint64) if with_pos else None)
+        pp, npos, _ = _ptr(pos, np.uint64) if with_pos else (None, 0, None)
+        if out_pos is not None and npos < cap:
+            raise ValueError("minimizer: out_pos is shorter than out")
         n = C.c_uint64()
         _check(self.L.ukm_minimizer(self.h, pb, poff, noff - 1, k, w, int(circular), max_hash, po, pp, cap,
-                                    C.byref(n)))
+                                    C.byref(n)), n.value)
         return (out[: n.value], pos[: n.value]) if with_pos else out[: n.value]
 
     def count(self, bases, rec_off, k, canonical=True, circular=False, hashed=False, max_hash=0, mode=UNIQUE, out=None):
@@ -375,28 +388,32 @@ class Context:
         po, cap, _ = _ptr(out, np.uint64)
         n = C.c_uint64()
         _check(self.L.ukm_count(self.h, pb, poff, noff - 1, int(k), int(canonical), int(circular), int(hashed), int(max_hash), int(mode), po,
-                                cap, C.byref(n)))
+                                cap, C.byref(n)), n.value)
         return out[: n.value]
 
     def max_hash(self, scale):
         return self.L.ukm_max_hash(scale)
 
     # ---- k-mers back to the genome ----
-    def _coords(self, call, ref, dtypes, out_cap):
+    def _coords(self, call, ref, dtypes, out_cap, given=None):
         """run call(pointers, cap, n) with caller-side outputs of `out_cap` entries; with out_cap None: a first guess, and
-        the exact size the library reports (UKM_ERR_CAPACITY, n_out) for the one repeat"""
+        the exact size the library reports (UKM_ERR_CAPACITY, n_out) for the one repeat.  given: the caller's own arrays,
+        all of one length (that length is the capacity)"""
+        if given is not None:
+            out_cap = _ptr(given[0], dtypes[0])[1]
+            assert len(given) == len(dtypes) and all(_ptr(o, dt)[1] == out_cap for o, dt in zip(given, dtypes))
         cap = (1 << 16) if out_cap is None else int(out_cap)
         for attempt in (0, 1):
-            outs = [_empty_like_kind(ref, cap, dt) for dt in dtypes]
+            outs = list(given) if given is not None else [_empty_like_kind(ref, cap, dt) for dt in dtypes]
             n = C.c_uint64()
             rc = call([_ptr(o, dt)[0] for o, dt in zip(outs, dtypes)], cap, n)
             if rc == ERR_CAPACITY and out_cap is None and attempt == 0:
                 cap = int(n.value)
                 continue
-            _check(rc)
+            _check(rc, n.value)
             return tuple(o[: n.value] for o in outs)
 
-    def locate(self, bases, rec_off, k, q_keys, circular=False, hashed=False, out_cap=None):
+    def locate(self, bases, rec_off, k, q_keys, circular=False, hashed=False, out_cap=None, outs=None):
         """`unikmer locate` (locate.go:141-289): every occurrence of every queried code.  Returns (q, rec, pos): index into
         q_keys, record index, window index in the record; queries in q_keys order (a code only where it first appears),
         a query's windows ascending."""
@@ -405,9 +422,9 @@ class Context:
         pq, nq, k3 = _ptr(q_keys, np.uint64)
         return self._coords(lambda o, cap, n: self.L.ukm_locate(self.h, pb, poff, noff - 1, int(k), int(circular), int(hashed), pq, nq,
                                                                 o[0], o[1], o[2], cap, C.byref(n)),
-                            bases, (np.uint64, np.uint32, np.uint64), out_cap)
+                            bases, (np.uint64, np.uint32, np.uint64), out_cap, outs)
 
-    def map(self, bases, rec_off, genome_off, k, set_keys, hashed=False, allow_multi=False, min_len=200, out_cap=None):
+    def map(self, bases, rec_off, genome_off, k, set_keys, hashed=False, allow_multi=False, min_len=200, out_cap=None, outs=None):
         """`unikmer map` / `uniqs` at -x 0 -X 0 (map.go:116-491): regions covered by k-mers of the sorted set.  Returns
         (rec, start, end) per region, in record then position order.  genome_off groups records into genomes
         (None: every record its own genome)."""
@@ -419,7 +436,7 @@ class Context:
         ps, ns, k4 = _ptr(set_keys, np.uint64)
         return self._coords(lambda o, cap, n: self.L.ukm_map(self.h, pb, poff, noff - 1, pg, ng - 1, int(k), int(hashed), ps, ns,
                                                              int(allow_multi), int(min_len), o[0], o[1], o[2], cap, C.byref(n)),
-                            bases, (np.uint32, np.uint64, np.uint64), out_cap)
+                            bases, (np.uint32, np.uint64, np.uint64), out_cap, outs)
 
     # ---- record selection (grep / filter / sample): kept records in input order, taxids copied ----
     def _select(self, call, keys, taxids, bound, out, out_taxids):
@@ -437,7 +454,7 @@ class Context:
         po, cap, _ = _ptr(out, np.uint64)
         pot, _, _ = _ptr(out_taxids if per_record else None, np.uint32)
         m = C.c_uint64()
-        _check(call(pk, pt, n, po, pot, cap, C.byref(m)))
+        _check(call(pk, pt, n, po, pot, cap, C.byref(m)), m.value)
         return (out[: m.value], out_taxids[: m.value]) if per_record else out[: m.value]
 
     def grep(self, keys, queries=None, query_taxids=None, taxids=None, canonical_k=0, invert=False, out=None, out_taxids=None):
@@ -498,7 +515,7 @@ class Context:
         po, cap, _ = _ptr(out, np.uint64)
         pot, _, _ = _ptr(out_taxids, np.uint32)
         m = C.c_uint64()
-        _check(self.L.ukm_unique(self.h, pk, pt, n, mode, po, pot, cap, C.byref(m)))
+        _check(self.L.ukm_unique(self.h, pk, pt, n, mode, po, pot, cap, C.byref(m)), m.value)
         return (out[: m.value], out_taxids[: m.value]) if taxids is not None else out[: m.value]
 
     # ---- set operations ----
@@ -521,7 +538,7 @@ class Context:
         po, cap, _ = _ptr(out, np.uint64)
         pot, _, _ = _ptr(out_taxids, np.uint32)
         n = C.c_uint64()
-        _check(self.L.ukm_setop2_ft(self.h, op, pa, pta, fa, na, pb, ptb, fb, nb, flags, po, pot, cap, C.byref(n)))
+        _check(self.L.ukm_setop2_ft(self.h, op, pa, pta, fa, na, pb, ptb, fb, nb, flags, po, pot, cap, C.byref(n)), n.value)
         return (out[: n.value], out_taxids[: n.value]) if tax else out[: n.value]
 
     def stream_table(self, keys_list, taxids_list=None):
@@ -611,7 +628,7 @@ class Context:
         else:
             mode, final_round = extra
             rc = L.ukm_merge_k_ft(self.h, kpp, tpp, pft, lens, n, mode, int(final_round), po, pot, cap, C.byref(m))
-        _check(rc)
+        _check(rc, m.value)
         return (out[: m.value], out_taxids[: m.value]) if tax else out[: m.value]
 
     def union(self, keys_list, taxids_list=None, out=None, out_taxids=None):
