@@ -143,11 +143,15 @@ int ukm_last_route(ukm_ctx *ctx);
  *        clade codes in the probe tables / the single pass's emit never / always;
  *        "grep_lds" 0 / 1 ukm_grep by codes: the queries never / whenever they fit (2048 of them) in an LDS table per
  *        workgroup instead of sorted behind a prefix directory.
+ *      Developer / test keys: "ws_poison" b (0..255) fills the whole device workspace with byte b before every
+ *        call, so that a kernel reading a workspace word it never initialised cannot pass by luck; unset: nothing is enqueued.
  *      The environment is read ONCE, when a context is created: every UKM_* variable present then is the context's default
  *      for the matching key; no compute call calls getenv (a context created under UKM_ENV_LIVE=1 -- the test suite, which
  *      flips knobs between calls -- keeps looking).  An explicitly set option always wins.
  *      ukm_ctx_get_stat: "punion_attempts" = base sets the last hash-probe union / counting-probe call built (2: its retry
- *      with four times the files ran), "workspace_bytes" = device workspace currently held by the context, "sort_fused_hist" = sorts of this context whose first
+ *      with four times the files ran), "workspace_bytes" = device workspace currently held by the context, "workspace_blocks" = the allocations it consists of,
+ *      "ws_poisoned_bytes" = bytes option "ws_poison" has filled since the most recent call began (the blocks that call created, the
+ *      block they were merged into when it ended and a later ukm_ctx_reserve included; the next call starts from zero), "sort_fused_hist" = sorts of this context whose first
  *      digit histogram came from the kernel that produced the keys (ukm_count) instead of a pass of their own, "grep_route" =
  *      the membership shape of the last ukm_grep (1 LDS table, 2 prefix directory, 3 taxid bitmap, 0 no kernel ran). */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);

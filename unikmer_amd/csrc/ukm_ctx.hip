@@ -41,6 +41,8 @@ static const char *const UKM_OPTION_KEYS[] = {
     // tuning / diagnostics (developer)
     "punion_k0", "punion_claim", "punion_debug", "kway_k", "kway_r", "kway_top2", "kway_debug", "srmerge_fill", "srmerge_spr", "srmerge_buckets",
     "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_fix", "map_dir_slack",
+    // test aid: the byte every arena block is filled with before a top-level call (see ws_poison_fill)
+    "ws_poison",
 };
 
 static std::string knob_name(const char *key) {
@@ -61,10 +63,20 @@ const char *ukm_env(const ukm_ctx *c, const char *name) {
     return getenv(name);  // (no context, or a context created under UKM_ENV_LIVE=1: the test suite)
 }
 
+// the byte of knob UKM_WS_POISON, -1 when it is unset (or no byte)
+static int ws_poison_knob(const ukm_ctx *c) {
+    const int v = ukm_env_int(c, "UKM_WS_POISON", -1);
+    return v >= 0 && v <= 255 ? v : -1;
+}
+
 extern "C" int ukm_ctx_set_option(ukm_ctx *c, const char *key, long long value) {
     if (!c || !key) UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_set_option: NULL argument");
     for (const char *k : UKM_OPTION_KEYS)
         if (strcmp(k, key) == 0) {
+            if (strcmp(key, "ws_poison") == 0) {
+                if (value < 0 || value > 255) UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_set_option: ws_poison is a byte, 0..255 (got %lld)", value);
+                c->ws_poison = (int)value;
+            }
             c->opts[knob_name(key)] = std::to_string(value);
             // (the watchdog's latch is a fact about the device, not an option: clearing the option never clears it)
             if (strcmp(key, "force_ticket") == 0) c->setop_force_ticket = c->ticket_latched || value != 0;
@@ -77,6 +89,7 @@ extern "C" int ukm_ctx_unset_option(ukm_ctx *c, const char *key) {
     if (!c || !key) UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_unset_option: NULL argument");
     c->opts.erase(knob_name(key));
     if (strcmp(key, "force_ticket") == 0) c->setop_force_ticket = c->ticket_latched || ukm_env_is(c, "UKM_FORCE_TICKET", '1');
+    if (strcmp(key, "ws_poison") == 0) c->ws_poison = ws_poison_knob(c);
     return UKM_OK;
 }
 
@@ -98,7 +111,9 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
         u64 t = 0;
         for (auto &b : c->blocks) t += b.cap;
         *value = t;
-    } else UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_get_stat: unknown statistic '%s'", key);
+    } else if (strcmp(key, "workspace_blocks") == 0) *value = c->blocks.size();
+    else if (strcmp(key, "ws_poisoned_bytes") == 0) *value = c->stat_ws_poisoned;
+    else UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_get_stat: unknown statistic '%s'", key);
     return UKM_OK;
 }
 
@@ -139,6 +154,7 @@ extern "C" int ukm_ctx_create(int device, ukm_ctx **out) {
     c->env_live = ukm_env_is(c, "UKM_ENV_LIVE", '1');
     // developer/test knob: exercise the ticketed (dispatch-order independent) set-op kernel
     c->setop_force_ticket = ukm_env_is(c, "UKM_FORCE_TICKET", '1');
+    c->ws_poison = ws_poison_knob(c);
     *out = c;
     return UKM_OK;
 }
@@ -208,6 +224,16 @@ extern "C" int ukm_ctx_sync(ukm_ctx *c) {
 static const size_t WS_ALIGN = 256;
 static const size_t WS_MIN_BLOCK = (size_t)64 << 20;
 
+// Test aid (option "ws_poison"): fill a whole arena block with the poison byte, on the context's stream.  A block is
+// filled when it is created and again before every top-level call, so that no kernel of a call finds a workspace word
+// that an earlier call, or a fresh allocation, happened to leave in a useful state.  Never inside a call: live data of
+// the call sits in the arena then.
+static int ws_poison_fill(ukm_ctx *c, const WsBlock &b) {
+    UKM_HIP(hipMemsetAsync(b.base, c->ws_poison, b.cap, c->stream));
+    c->stat_ws_poisoned += b.cap;
+    return UKM_OK;
+}
+
 static int ws_new_block(ukm_ctx *c, size_t need) {
     size_t total = 0;
     for (auto &b : c->blocks) total += b.cap;
@@ -225,6 +251,7 @@ static int ws_new_block(ukm_ctx *c, size_t need) {
                  hipGetErrorString(e));
     }
     c->blocks.push_back(WsBlock{(char *)p, cap, 0});
+    if (c->ws_poison >= 0) UKM_TRY(ws_poison_fill(c, c->blocks.back()));
     return UKM_OK;
 }
 
@@ -269,9 +296,10 @@ static int ws_reset_top(ukm_ctx *c) {
         size_t want = c->ws_high + (c->ws_high >> 3) + WS_ALIGN * 64;
         ws_free_all(c);
         void *p = nullptr;
-        if (hipMalloc(&p, want) == hipSuccess)
+        if (hipMalloc(&p, want) == hipSuccess) {
             c->blocks.push_back(WsBlock{(char *)p, want, 0});
-        else
+            if (c->ws_poison >= 0) (void)ws_poison_fill(c, c->blocks.back());  // (a created block, like ws_new_block's)
+        } else
             (void)hipGetLastError();
     }
     for (auto &b : c->blocks) b.used = 0;
@@ -304,6 +332,7 @@ extern "C" int ukm_ctx_reserve(ukm_ctx *c, uint64_t bytes) {
                  hipGetErrorString(e));
     }
     c->blocks.push_back(WsBlock{(char *)p, (size_t)bytes, 0});
+    if (c->ws_poison >= 0) UKM_TRY(ws_poison_fill(c, c->blocks.back()));
     return UKM_OK;
 }
 
@@ -373,6 +402,14 @@ int ukm_begin(ukm_ctx *c, CallScope *s) {
             UKM_FAIL(UKM_ERR_HIP, "hipSetDevice(%d): %s", c->device, hipGetErrorString(e));
         }
         c->copybacks.clear();
+        if (c->ws_poison >= 0) {  // before anything else of the call
+            c->stat_ws_poisoned = 0;
+            for (auto &b : c->blocks)
+                if (ws_poison_fill(c, b) != UKM_OK) {
+                    c->depth--;
+                    return UKM_ERR_HIP;
+                }
+        }
         (void)hipEventRecord(c->ev_start, c->stream);
         c->ev_valid = false;
         c->evk_valid = false;

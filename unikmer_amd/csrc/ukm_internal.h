@@ -115,6 +115,11 @@ struct ukm_ctx {
 
     std::vector<WsBlock> blocks;
     size_t ws_high = 0;  // high-water mark of one top-level call, for consolidation
+    // test aid (option "ws_poison"): the byte every arena block is filled with before a top-level call and when it is
+    // created; -1 = off, and nothing is enqueued.  stat_ws_poisoned: the bytes filled since the most recent top-level call
+    // began (the blocks it created, the block ws_reset_top merged them into and a later ukm_ctx_reserve included)
+    int ws_poison = -1;
+    u64 stat_ws_poisoned = 0;
 
     // pending host copy-backs of the current top-level call
     struct CopyBack {

@@ -268,6 +268,41 @@ class Context:
         """give the device workspace back (it is kept at the size the largest call needed)"""
         _check(self.L.ukm_ctx_trim(self.h))
 
+    # device / pinned host memory and copies (include/unikmer_hip.h).  Pointers are plain integers; `dst` / `src` of the
+    # copies are such integers (or anything C.c_void_p takes), `nbytes` bytes each.
+    def dev_alloc(self, nbytes):
+        p = C.c_void_p()
+        _check(self.L.ukm_dev_alloc(self.h, nbytes, C.byref(p)))
+        return p.value
+
+    def dev_free(self, ptr):
+        _check(self.L.ukm_dev_free(self.h, C.c_void_p(ptr)))
+
+    def copy(self, dst, src, nbytes):
+        """synchronous copy on the context's stream, any direction"""
+        _check(self.L.ukm_copy(self.h, C.c_void_p(dst), C.c_void_p(src), nbytes))
+
+    def host_alloc(self, nbytes):
+        """pinned host memory: what copy_async needs to overlap with compute"""
+        p = C.c_void_p()
+        _check(self.L.ukm_host_alloc(self.h, nbytes, C.byref(p)))
+        return p.value
+
+    def host_free(self, ptr):
+        _check(self.L.ukm_host_free(self.h, C.c_void_p(ptr)))
+
+    def copy_async(self, dst, src, nbytes):
+        """copy on the context's transfer stream, ordered behind the compute calls issued so far"""
+        _check(self.L.ukm_copy_async(self.h, C.c_void_p(dst), C.c_void_p(src), nbytes))
+
+    def copy_fence(self):
+        """compute calls issued after the fence start after the transfers issued before it"""
+        _check(self.L.ukm_copy_fence(self.h))
+
+    def copy_sync(self):
+        """wait for the transfers issued so far"""
+        _check(self.L.ukm_copy_sync(self.h))
+
     def last_kernel_ms(self):
         ms = C.c_float()
         _check(self.L.ukm_last_kernel_ms(self.h, C.byref(ms)))
