@@ -153,7 +153,15 @@ int ukm_last_route(ukm_ctx *ctx);
  *      "ws_poisoned_bytes" = bytes option "ws_poison" has filled since the most recent call began (the blocks that call created, the
  *      block they were merged into when it ended and a later ukm_ctx_reserve included; the next call starts from zero), "sort_fused_hist" = sorts of this context whose first
  *      digit histogram came from the kernel that produced the keys (ukm_count) instead of a pass of their own, "grep_route" =
- *      the membership shape of the last ukm_grep (1 LDS table, 2 prefix directory, 3 taxid bitmap, 0 no kernel ran). */
+ *      the membership shape of the last ukm_grep (1 LDS table, 2 prefix directory, 3 taxid bitmap, 0 no kernel ran),
+ *      "count_window_retries" = ukm_count calls of this context that ran their window pass twice (more windows passed the
+ *      Scaled filter than the size estimate of the internal buffer allowed for; the second pass is sized exactly),
+ *      "punion_flags" = the flag word the most recent hash-probe pass of this context left (union, union of files with one
+ *      taxid each, counting probes of `common`; 0 when none has run, and cleared when a call tries such a route, so that
+ *      an attempt that declines in front of its pass shows 0 and not an earlier call's word): 1 PU_FLAG_UNSORTED a file is not sorted, 2
+ *      PU_FLAG_OVERFLOW the list of records the base set lacks outgrew its estimated size (stores are guarded), 4
+ *      PU_FLAG_TAXID a taxid outside the loaded taxonomy, 8 PU_FLAG_RAW a record no table could take.  Any bit makes the
+ *      route decline without having written the output, and the general merge answers the call. */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);
@@ -209,7 +217,11 @@ uint64_t ukm_max_hash(uint64_t scale);
  *      set), UKM_REPEATED (`-d`: codes seen at least twice) or UKM_SINGLETON (`-u`: exactly once), sorted ascending (`-s`).
  *      The windows stay in the context's device workspace (8 B per base while the call runs); only the result is written to
  *      out[out_cap] (host or device).  The same result as ukm_encode_kmers / ukm_nthash + ukm_sort_u64 + ukm_unique with one
- *      stream synchronisation instead of three.  Too small an out_cap: UKM_ERR_CAPACITY, *n_out = the size needed. */
+ *      stream synchronisation instead of three.  Too small an out_cap: UKM_ERR_CAPACITY, *n_out = the size needed.
+ *      UKM_ERR_CAPACITY speaks about out_cap ONLY: out never needs more than the result's size, however many windows pass
+ *      the filter.  The internal window buffer of a Scaled sketch is sized from an estimate; input that defeats it (a
+ *      low-complexity record whose one hash lies below max_hash) costs a second window pass into a buffer of the exact
+ *      size (stat "count_window_retries"), never an error. */
 int ukm_count(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, int k, int canonical,
               int circular, int hashed, uint64_t max_hash, int mode, uint64_t *out, uint64_t out_cap, uint64_t *n_out);
 

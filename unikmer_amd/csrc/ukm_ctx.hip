@@ -105,6 +105,8 @@ extern "C" int ukm_ctx_get_option(ukm_ctx *c, const char *key, long long *value,
 extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long *value) {
     if (!c || !key || !value) UKM_FAIL(UKM_ERR_INVALID, "ukm_ctx_get_stat: NULL argument");
     if (strcmp(key, "punion_attempts") == 0) *value = c->stat_punion_attempts;
+    else if (strcmp(key, "punion_flags") == 0) *value = c->stat_punion_flags;
+    else if (strcmp(key, "count_window_retries") == 0) *value = c->stat_count_window_retries;
     else if (strcmp(key, "sort_fused_hist") == 0) *value = c->stat_sort_fused_hist;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "workspace_bytes") == 0) {

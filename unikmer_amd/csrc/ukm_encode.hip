@@ -1535,16 +1535,32 @@ extern "C" int ukm_count(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec
             const double keep = 2.0 * ((double)max_hash / 18446744073709551615.0);  // canonical = the smaller of two hashes
             wcap = std::min<u64>(wcap, (u64)((double)total_bases * std::min(1.0, 1.5 * keep)) + (1u << 20));
         }
-        u64 *w = nullptr;
-        UKM_TRY(ws_alloc_t(ctx, (size_t)wcap, &w));
+        const bool estimated = wcap < total_bases + 1;
         int bits = hashed ? 64 : 2 * k;
         if (hashed && max_hash && max_hash != ~0ull) bits = 64 - __builtin_clzll(max_hash);
         // the sort's first histogram is counted by the kernel that writes the windows (the strip kernel, when it runs)
         FusedHist fh = {nullptr, bits, -1};
         UKM_TRY(ws_alloc_t(ctx, 256, &fh.hist));
-        UKM_HIP(hipMemsetAsync(fh.hist, 0, 256 * sizeof(u64), ctx->stream));
+        const WsMark before_w = ws_mark(ctx);
+        u64 *w = nullptr;
         u64 nw = 0;
-        UKM_TRY(run_windows(ctx, hashed != 0, b, off, n_rec, k, canonical, circular, max_hash, w, wcap, &nw, total_bases, nullptr, &fh));
+        for (int pass = 0;; pass++) {
+            UKM_TRY(ws_alloc_t(ctx, (size_t)wcap, &w));
+            UKM_HIP(hipMemsetAsync(fh.hist, 0, 256 * sizeof(u64), ctx->stream));
+            fh.shift = -1;
+            const int rw = run_windows(ctx, hashed != 0, b, off, n_rec, k, canonical, circular, max_hash, w, wcap, &nw, total_bases, nullptr, &fh);
+            // More windows passed the Scaled filter than the estimate allowed for (a low-complexity record whose one hash lies
+            // below max_hash): the buffer is the library's own, so this is not the caller's UKM_ERR_CAPACITY.  The filter
+            // kernel has counted past the cap with its stores guarded and run_windows has read the count back (the stream is
+            // idle): the pass runs once more into a buffer of exactly that size.
+            if (rw != UKM_ERR_CAPACITY || !estimated || pass > 0 || nw <= wcap) {
+                UKM_TRY(rw);
+                break;
+            }
+            ctx->stat_count_window_retries++;
+            ws_release(ctx, before_w);
+            wcap = nw;
+        }
         if (nw == 0) {
             ukm_out_resize(ctx, out, 0);
             return UKM_OK;

@@ -159,6 +159,8 @@ struct ukm_ctx {
     // statistics a host or a test may ask for (ukm_ctx_get_stat)
     u64 stat_grep_route = 0;  // membership shape of the last ukm_grep: 1 queries in LDS, 2 sorted queries behind a prefix directory, 3 taxid bitmap, 0 no kernel
     u64 stat_punion_attempts = 0;  // base sets the last probe union / counting probes built (2: the retry with 4 x the files ran)
+    u64 stat_punion_flags = 0;     // the flag word (ctl[1], PU_FLAG_*) the most recent probe pass of this context left
+    u64 stat_count_window_retries = 0;  // ukm_count calls that repeated the window pass: its estimated buffer was too small
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device
     bool setop_force_ticket = false;  // = ticket_latched || option "force_ticket"

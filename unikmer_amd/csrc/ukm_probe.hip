@@ -276,6 +276,7 @@ int ukm_pu_base_union(ukm_ctx *c, const UkmStreams &b, u64 **base, u32 **base_ta
 
 int ukm_pu_attempts(ukm_ctx *c, int k0, int S, double min_hit, bool *low_hit, const std::function<int(int, bool *, double *)> &attempt) {
     c->stat_punion_attempts = 0;
+    c->stat_punion_flags = 0;  // (an attempt that declines in front of its probe pass leaves no earlier call's flags behind)
     for (int n = 0;; n++) {
         const WsMark m = ws_mark(c);
         c->stat_punion_attempts++;

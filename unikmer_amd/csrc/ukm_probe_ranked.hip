@@ -585,6 +585,7 @@ int ukm_probe_union_ranked(ukm_ctx *c, const UkmStreams &in, int k0, const UkmOu
     //  them is in the list instead --, so the entry, the base set's last, stays out of the final union)
     u64 last = 0;
     UKM_TRY(ukm_read_u64(c, ctl, h, 2));
+    c->stat_punion_flags = h[1];
     UKM_TRY(ukm_read_u64(c, base + n0 - 1, &last));
     if (lap.on) fprintf(stderr, "[punion/ranked] S=%d n0=%llu R=%u range=%u records=%llu listed=%llu (cap %llu) flags=%llu\n", S, (unsigned long long)n0,
                         a.R, a.range, (unsigned long long)total, (unsigned long long)h[0], (unsigned long long)miss_cap, (unsigned long long)h[1]);

@@ -874,6 +874,7 @@ static int probe_union_k0(ukm_ctx *c, const UkmStreams &in, int k0, const UkmOut
     }));
     if (heavy) return UKM_OK;
     UKM_TRY(ukm_read_u64(c, ctl, h, 2));
+    c->stat_punion_flags = h[1];
     if (lap.on) fprintf(stderr, "[punion] S=%d n0=%llu R=%u later=%llu misses=%llu (cap %llu) flags=%llu\n", S, (unsigned long long)n0,
                         a.R, (unsigned long long)later, (unsigned long long)h[0], (unsigned long long)miss_cap, (unsigned long long)h[1]);
     if (h[1] != 0) return UKM_OK;  // unsorted input / overflow: the general route reports or handles it
@@ -922,6 +923,7 @@ int ukm_dev_probe_common(ukm_ctx *c, const UkmStreams &in, u32 threshold, bool f
     *declined = true;
     *o.n = 0;
     const int mode = ukm_punion_mode(c);
+    c->stat_punion_flags = 0;  // (as ukm_pu_attempts does for the union: the flags of THIS call's probe pass, or none)
     if (mode == 0 || S < 3 || S > PU_MAXS || in.lens[0] == 0) return UKM_OK;
     u64 later = 0;
     for (int j = 1; j < S; j++) later += in.lens[j];
@@ -1025,6 +1027,7 @@ int ukm_dev_probe_common(ukm_ctx *c, const UkmStreams &in, u32 threshold, bool f
     UKM_HIP(hipGetLastError());
     u64 h[2] = {0, 0};
     UKM_TRY(ukm_read_u64(c, ctl, h, 2));
+    c->stat_punion_flags = h[1];
     if (dbg) fprintf(stderr, "[pcommon] S=%d n0=%llu R=%u later=%llu threshold=%u out=%llu flags=%llu\n", S, (unsigned long long)n0, a.R,
                      (unsigned long long)later, threshold, (unsigned long long)h[0], (unsigned long long)h[1]);
     if (h[1] != 0) return UKM_OK;
