@@ -182,6 +182,12 @@ int ukm_taxonomy_load(ukm_ctx *ctx, const uint32_t *child, const uint32_t *paren
                       const uint32_t *merged_old, const uint32_t *merged_new, uint64_t m);
 int ukm_taxonomy_max_taxid(ukm_ctx *ctx, uint32_t *max_taxid); /* taxdump.MaxTaxid, util.go:169 */
 int ukm_lca(ukm_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t *out);
+/* rank of every node: rank_id[i] in 1..255 names the rank of child[i] (the host numbers the rank strings of
+ * nodes.dmp's third column, lower-cased); 0 = this node has no known rank.  Needs a loaded taxonomy
+ * (UKM_ERR_NO_TAXONOMY); a child that is not a node of it: UKM_ERR_INVALID, nothing changed.  Nodes the call does not
+ * name keep rank id 0 (a second call replaces the whole column).  One byte per id on the device.
+ * ukm_taxonomy_load drops the ranks together with the tables it replaces. */
+int ukm_taxonomy_set_ranks(ukm_ctx *ctx, const uint32_t *child, const uint8_t *rank_id, uint64_t n);
 
 /* ---- encode: replaces sketches.NewKmerIterator(seq,k,canonical,circular).NextKmer()
  *      (count.go:321,363) = kmers v0.1.0 2-bit encode + canonical.
@@ -296,6 +302,62 @@ int ukm_filter(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint6
                uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
 int ukm_sample(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n, uint64_t start,
                uint64_t window, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
+
+/* ---- filter by taxonomic rank: replaces newRankFilter + isPassed (rfilter.go:371-520) and the record loop of `unikmer rfilter`
+ *      (rfilter.go:280-304).  The host reads the rank file (readRankOrderFromFile, rfilter.go:522-580), numbers the rank
+ *      strings 1..255 (ukm_taxonomy_set_ranks) and states the filter in those numbers: */
+typedef struct ukm_rank_filter {
+    int32_t order[256];   /* > 0: rank id r is in the rank file's ordered list, larger = higher rank (the file's LAST
+                             line has 1: rfilter.go:566-578); 0: r has no order ("!" ranks, rank id 0) */
+    uint8_t no_rank[256]; /* 1: r is a "!" rank of the rank file */
+    uint8_t black[256];   /* 1: r is on -B/--black-list */
+    int32_t lower, higher;/* the ORDER of -L / -H, 0 = not given; both given: UKM_ERR_INVALID */
+    int32_t equal[32]; int32_t n_equal;   /* the orders of -E */
+    uint8_t discard_norank, save_norank, discard_root;  /* -N, -n, -R */
+    uint32_t root_taxid;  /* --root-taxid */
+} ukm_rank_filter;
+/*      What happens to a record with taxid t -- isPassed as it is written, quirks included, in this order:
+ *       1. discard_root and t == root_taxid: dropped.  The comparison is on the record's taxid as given.
+ *       2. t at or beyond the table (above the largest id of the loaded dumps), t == 0, absent from the taxonomy, or of rank
+ *          id 0: dropped (the reference's `Rank() == ""`).  A MERGED id is looked up as its target and a walk (6) starts
+ *          from the target, as in ukm_lca; taxdump is not in the reference tree, so what its Rank does with a merged id is
+ *          unpinned: this is the build's own contract.  Below, r = the rank id of t (of its target).
+ *       3. black[r]: dropped.
+ *       4. no_rank[r] and discard_norank: without save_norank dropped; with save_norank and lower != 0 the WALK (6) decides;
+ *          with save_norank and lower == 0 the record goes on to 5 (newRankFilter does not refuse that, only the command
+ *          line does).
+ *       5. o = order[r] (0 for a rank without order; order[0] is never looked at).  o among equal[0 .. n_equal): kept.
+ *          Otherwise with lower: kept when o < lower -- so a rank without order that 4 did not discard passes under -L; with
+ *          higher: kept when o > higher; with neither: kept only when n_equal == 0.
+ *       6. WALK (rfilter.go:469-491): p = parent[t]; then repeatedly: p == 1 (the literal 1 of the reference, not
+ *          root_taxid, and tested BEFORE p's own rank is looked at): dropped; p absent: dropped; order[rank of p] > 0: kept
+ *          when that order is <= lower (not <), dropped otherwise; parent[p] == p: dropped; else p = parent[p].  The two
+ *          drops at an absent node and at a root other than 1 stand where the reference would loop for ever; wherever the
+ *          reference terminates the results are the same.
+ *      A record's fate depends on its taxid alone: one kernel over the taxonomy writes one keep bit per taxid (once per
+ *      call), and the selection kernel of ukm_grep by taxid reads that bitmap.
+ *      ukm_rank_filter_plan: 1-5 as a pure host function (no context, no device): what a taxid of rank r meets, as two
+ *      256-byte tables.  self_action[r]: 0 dropped, 1 kept, 2 decided by the walk.  walk_action[r] for an ancestor of rank r:
+ *      0 go on, 1 kept, 2 dropped.  lower and higher both non-zero, or n_equal outside 0..32: UKM_ERR_INVALID.
+ *      ukm_rank_pass: out[i] = 1 when a record with taxids[i] is kept, else 0.  Host or device pointers, as ukm_lca.
+ *      ukm_rfilter: the conventions of ukm_grep by taxid -- input order, duplicates kept, each record with its own taxid;
+ *      taxids == NULL: every record carries file_taxid (a copy or an empty result); the size query and UKM_ERR_CAPACITY as
+ *      everywhere.  Both need a taxonomy WITH ranks: UKM_ERR_NO_TAXONOMY otherwise. */
+int ukm_rank_filter_plan(const ukm_rank_filter *f, uint8_t self_action[256], uint8_t walk_action[256]);
+int ukm_rank_pass(ukm_ctx *ctx, const ukm_rank_filter *f, const uint32_t *taxids, uint64_t n, uint8_t *out);
+int ukm_rfilter(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint32_t file_taxid, uint64_t n,
+                const ukm_rank_filter *f, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
+
+/* ---- split by taxid: replaces the map of `unikmer tsplit` (tsplit.go:112-192): the records grouped by taxid, groups in
+ *      ASCENDING taxid order (the reference's order is Go's map order, i.e. none), inside a group the codes in INPUT order
+ *      (stable).  taxids[n] is required (a host with a file that has one global taxid needs no call).  out_keys[out_cap]:
+ *      needs n.  group_taxids[group_cap], group_off[group_cap + 1]: group g is out_keys[group_off[g] .. group_off[g + 1]),
+ *      group_off[n_groups] = n.  out_cap < n or group_cap < the number of groups: UKM_ERR_CAPACITY, *n_groups = the number
+ *      of groups, nothing outside the capacities written; out_cap == 0 && group_cap == 0 is the size query (outputs may be
+ *      NULL).  n == 0: UKM_OK, 0 groups, group_off untouched.  n >= 2^32: UKM_ERR_INVALID (record indices are the sort's
+ *      32-bit payload).  No taxonomy is needed: taxids are plain numbers here, 0 and 2^32 - 1 included. */
+int ukm_tsplit(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n, uint64_t *out_keys, uint64_t out_cap,
+               uint32_t *group_taxids, uint64_t *group_off, uint64_t group_cap, uint64_t *n_groups);
 
 /* ---- k-way merge: replaces mergeChunksFile (util-sort.go:227-606).  Streams are expected
  *      to be sorted (chunk files); an unsorted one is tolerated (the call then sorts the

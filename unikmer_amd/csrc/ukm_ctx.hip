@@ -175,6 +175,7 @@ extern "C" int ukm_ctx_destroy(ukm_ctx *c) {
     if (c->tax_parent) (void)hipFree(c->tax_parent);
     if (c->tax_depth) (void)hipFree(c->tax_depth);
     if (c->tax_merged) (void)hipFree(c->tax_merged);
+    if (c->tax_rank) (void)hipFree(c->tax_rank);
     if (c->tax_anc) (void)hipFree(c->tax_anc);
     if (c->tax_euler) (void)hipFree(c->tax_euler);
     if (c->tax_node_at) (void)hipFree(c->tax_node_at);

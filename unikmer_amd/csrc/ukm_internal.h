@@ -50,6 +50,8 @@ struct TaxDev {
     const u8 *depth;    // dense [size]; root depth 0
     const u32 *merged;  // dense [size] or nullptr; 0 = not merged
     u32 size;
+    // (the rank column of ukm_taxonomy_set_ranks, dense u8 [size], lives beside these in the context -- ukm_ctx::tax_rank --
+    //  and is handed to the one kernel that reads it, ukm_tax.hip's rank_keep_kernel, as an argument of its own)
     // root-path table (round 3): anc[c * size + t] = the ancestors of t at depths 4c .. 4c+3 (t itself at its own
     // depth, 0 beyond it; all 0 for an absent taxid).  Always present when a taxonomy is loaded: ukm_taxonomy_load builds
     // every table or none (it refuses dumps whose dense tables do not fit the device).
@@ -133,6 +135,7 @@ struct ukm_ctx {
     u32 *tax_parent = nullptr;
     u8 *tax_depth = nullptr;
     u32 *tax_merged = nullptr;
+    u8 *tax_rank = nullptr;  // rank id of every node (ukm_taxonomy_set_ranks): dense [tax_size], 0 = no known rank; null until set
     uint4 *tax_anc = nullptr;  // root-path table, see TaxDev
     u32 *tax_euler = nullptr, *tax_node_at = nullptr;  // pre-order numbers, see TaxDev
     unsigned short *tax_clade = nullptr;                // clade codes, see TaxDev (tax_clade8: the one-byte form)
@@ -343,6 +346,9 @@ int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_
 int ukm_dev_fill_u32(ukm_ctx *c, u32 *dst, u64 n, u32 value);
 // decisions over per-file taxids on the device (ukm_tax.hip): plan[0] = inter's left LCA fold, plan[2 + j] = diff -t keeps
 int ukm_dev_ct_plan(ukm_ctx *c, const u32 *ct_host, int n, bool mix, u32 **plan);
+// the keep bitmap of a rank filter (ukm_tax.hip): bit t = a record with taxid t passes, t = 0 .. tax_size - 1, in an even number
+// of workspace words every one of which the kernel writes.  UKM_ERR_NO_TAXONOMY without a taxonomy or without ranks.
+int ukm_dev_rank_bitmap(ukm_ctx *c, const char *name, const ukm_rank_filter *f, u32 **bits);
 int ukm_dev_fill_u32_from(ukm_ctx *c, u32 *dst, u64 n, u32 value, const u32 *value_dev);  // value_dev != null: the value is read there
 // internal flag of ukm_dev_setop2 / _ct (op DIFF, first stream with duplicate codes): the survivors are NOT collapsed to one
 // record per code -- the caller is in the middle of an n-file fold (diff.go:437: mc1 = mc2 keeps every record; the map of

@@ -1,6 +1,7 @@
-// ukm_select.hip — order-preserving record selection: ukm_grep (grep.go:617-676), ukm_filter (filter.go:181-221) and
-// ukm_sample (sample.go:134-148).  On the device the first two are ONE operation: a predicate per record, the survivors
-// written in input order with their own taxids (copied, never folded: no taxonomy, no sorted input, every duplicate kept).
+// ukm_select.hip — order-preserving record selection: ukm_grep (grep.go:617-676), ukm_filter (filter.go:181-221),
+// ukm_sample (sample.go:134-148) and ukm_rfilter (rfilter.go:280-304).  On the device grep, filter and rfilter are ONE
+// operation: a predicate per record, the survivors written in input order with their own taxids (copied, never folded: no
+// sorted input, every duplicate kept; only rfilter's bitmap is built from a taxonomy).
 //
 // select_kernel<PRED, TAX, TICKET>: a tile is 256 threads x 8 consecutive records (16-byte loads where the arrays are
 // 16-byte aligned); the predicate answers all eight records of a thread at once (so that a membership predicate has eight
@@ -15,7 +16,8 @@
 //                  <= 0.5), built once per workgroup; the workgroup is PERSISTENT over tiles, lookups never leave the CU.
 //   GrepDir        the queries sorted and deduplicated on the device (ukm_dev_sort + ukm_dev_unique) behind the prefix
 //                  directory of ukm_dir.h: a directory pair plus a short search per record, as the window join of ukm_map.
-//   TaxidPred      one bit per taxid in 0 .. max queried taxid.
+//   TaxidPred      one bit per taxid in 0 .. max queried taxid (ukm_rfilter: the keep bitmap of the rank filter, one bit per
+//                  id of the taxonomy).
 // ukm_sample is a strided gather: no scan, no look-back.
 #include <algorithm>
 
@@ -460,6 +462,27 @@ int grep_taxids(ukm_ctx *c, const char *name, const u64 *k, const u32 *t, u32 fi
     return run_select(c, name, pred, k, t, n, out, tout, out_cap, n_out);
 }
 
+// the rank filter: a record's fate depends on its taxid alone -- one pass over the taxonomy writes a keep bit per taxid
+// (ukm_tax.hip), and the selection is grep by taxid over that bitmap
+int rfilter_taxids(ukm_ctx *c, const char *name, const u64 *k, const u32 *t, u32 file_taxid, u64 n, const ukm_rank_filter *f, u64 *out,
+                   u32 *tout, u64 out_cap, u64 *n_out) {
+    u32 *bits = nullptr;
+    UKM_TRY(ukm_dev_rank_bitmap(c, name, f, &bits));
+    const u32 max_taxid = c->tax_size - 1;
+    if (!t) {
+        bool hit = false;
+        if (file_taxid <= max_taxid) {
+            u64 w = 0;
+            UKM_TRY(ukm_read_u64(c, (const u64 *)bits + (file_taxid >> 6), &w));
+            hit = ((w >> (file_taxid & 63u)) & 1ull) != 0;
+        }
+        return hit ? copy_all(c, name, k, nullptr, n, out, nullptr, out_cap, n_out) : UKM_OK;
+    }
+    TaxidPred pred;
+    pred.bits = bits; pred.max_taxid = max_taxid; pred.invert = 0u;
+    return run_select(c, name, pred, k, t, n, out, tout, out_cap, n_out);
+}
+
 int filter_codes(ukm_ctx *c, const char *name, const u64 *k, const u32 *t, u64 n, int kk, int window, int ps, int pd, int threshold,
                  bool invert, u64 *out, u32 *tout, u64 out_cap, u64 *n_out) {
     if (window > kk) window = kk;  // filter.go:116-119
@@ -574,5 +597,21 @@ extern "C" int ukm_sample(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *ta
         UKM_HIP(hipGetLastError());
         *n_out = m;
         return UKM_OK;
+    });
+}
+
+extern "C" int ukm_rfilter(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint32_t file_taxid, uint64_t n,
+                           const ukm_rank_filter *f, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out) {
+    const char *name = "ukm_rfilter";
+    UKM_TRY(check_common(name, ctx, n_out, keys, taxids, n, out_keys, out_taxids, out_cap));
+    if (!f) UKM_FAIL(UKM_ERR_INVALID, "%s: NULL argument", name);
+    *n_out = 0;
+    if (!ctx->tax_parent || !ctx->tax_rank) UKM_FAIL(UKM_ERR_NO_TAXONOMY, "%s: no taxonomy with ranks loaded (ukm_taxonomy_set_ranks)", name);
+    {
+        uint8_t sa[256], wa[256];
+        UKM_TRY(ukm_rank_filter_plan(f, sa, wa));
+    }
+    return select_entry(ctx, keys, taxids, n, out_keys, out_taxids, out_cap, n_out, [&](const u64 *k, const u32 *t, u64 *out, u32 *tout) -> int {
+        return rfilter_taxids(ctx, name, k, t, file_taxid, n, f, out, tout, out_cap, n_out);
     });
 }

@@ -71,6 +71,62 @@ __global__ __launch_bounds__(256) void ct_plan_kernel(TaxDev T, const u32 *ct, u
     plan[1] = 0;
 }
 
+// ---- rank filter (ukm_rank_pass / ukm_rfilter; contract: include/unikmer_hip.h) -----------------------------------------
+// The decision tables of ukm_rank_filter_plan, as the builder kernel takes them (512 bytes of kernel arguments, copied into
+// LDS by the workgroup: they are indexed by a rank id read from memory).
+struct RankPlan {
+    u32 self_action[64];  // 256 bytes, byte r: 0 dropped, 1 kept, 2 the walk decides
+    u32 walk_action[64];  // 256 bytes, byte r: 0 go on, 1 kept, 2 dropped
+};
+constexpr int RANK_WALK_MAX = 256;  // (ukm_taxonomy_load refuses trees deeper than 250)
+
+// Thread t decides taxid t; a wave's 64 answers leave as two words of the bitmap, so every word of
+// the grid's 8 x gridDim is written (the bitmap needs no zeroing).  Only ids whose self action is 2 climb parent[].
+__global__ __launch_bounds__(256) void rank_keep_kernel(const u32 *parent, const u32 *merged, const u8 *rank, u32 size, RankPlan plan,
+                                                        u32 discard_root, u32 root_taxid, u32 *bits) {
+    __shared__ u32 s_plan[128];
+    const u32 tid = threadIdx.x;
+    if (tid < 64) s_plan[tid] = plan.self_action[tid];
+    else if (tid < 128) s_plan[tid] = plan.walk_action[tid - 64];
+    __syncthreads();
+    const u8 *s_self = reinterpret_cast<const u8 *>(s_plan), *s_walk = s_self + 256;
+    const u32 t = blockIdx.x * blockDim.x + tid;
+    bool keep = false;
+    if (t != 0 && t < size && !(discard_root && t == root_taxid)) {
+        u32 x = t;
+        if (parent[x] == 0) {  // absent: merged into another taxid? (as lca_dev resolves it)
+            const u32 m = merged ? merged[x] : 0u;
+            x = (m && m < size && parent[m] != 0) ? m : 0u;
+        }
+        const u32 act = x ? s_self[rank[x]] : 0u;
+        keep = act == 1;
+        if (act == 2) {
+            u32 p = parent[x];
+            for (int step = 0; step < RANK_WALK_MAX; step++) {
+                if (p == 1 || p >= size) break;
+                const u32 pp = parent[p];
+                if (pp == 0) break;
+                const u32 w = s_walk[rank[p]];
+                if (w) { keep = w == 1; break; }
+                if (pp == p) break;
+                p = pp;
+            }
+        }
+    }
+    const u64 mask = __ballot(keep);
+    const int lane = lane_id();
+    const u32 word = (t >> 6) * 2;  // (blockDim is a multiple of 64: a wave's ids share t >> 6)
+    if (lane == 0) bits[word] = (u32)mask;
+    if (lane == 32) bits[word + 1] = (u32)(mask >> 32);
+}
+
+__global__ void rank_pass_kernel(const u32 *bits, u32 size, const u32 *taxids, u64 n, u8 *out) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 t = taxids[i];
+    out[i] = t < size ? (u8)((bits[t >> 5] >> (t & 31u)) & 1u) : (u8)0;
+}
+
 // copy a (host or device) array to a host vector
 template <typename T>
 int to_host(ukm_ctx *c, const T *p, u64 n, std::vector<T> &v) {
@@ -90,7 +146,7 @@ int to_host(ukm_ctx *c, const T *p, u64 n, std::vector<T> &v) {
 // device bytes of the taxonomy a context holds now (credited when it is about to be replaced)
 static u64 tax_bytes_held(const ukm_ctx *c) {
     if (!c->tax_parent) return 0;
-    return (u64)c->tax_size * (sizeof(u32) + sizeof(u8) + (c->tax_merged ? sizeof(u32) : 0) + 2 * sizeof(u32) + (c->tax_clade ? 2 : (c->tax_clade8 ? 1 : 0))) +
+    return (u64)c->tax_size * (sizeof(u32) + sizeof(u8) + (c->tax_merged ? sizeof(u32) : 0) + (c->tax_rank ? sizeof(u8) : 0) + 2 * sizeof(u32) + (c->tax_clade ? 2 : (c->tax_clade8 ? 1 : 0))) +
            (u64)c->tax_nchunks * c->tax_size * sizeof(uint4) + (c->tax_pair ? ((u64)c->tax_kp * c->tax_kp + 4 + 5 * TAX_CPATH_ROWS) * sizeof(u32) : 0) +
            (c->tax_top ? (u64)c->tax_top_n * sizeof(uint4) : 0);
 }
@@ -357,6 +413,8 @@ extern "C" int ukm_taxonomy_load(ukm_ctx *c, const uint32_t *child, const uint32
             UKM_HIP(hipStreamSynchronize(c->stream));
             (void)hipFree(c->tax_parent); (void)hipFree(c->tax_depth);
             if (c->tax_merged) (void)hipFree(c->tax_merged);
+            if (c->tax_rank) (void)hipFree(c->tax_rank);
+            c->tax_rank = nullptr;
             (void)hipFree(c->tax_anc); (void)hipFree(c->tax_euler); (void)hipFree(c->tax_node_at);
             if (c->tax_clade) (void)hipFree(c->tax_clade);
             if (c->tax_top) (void)hipFree(c->tax_top);
@@ -434,6 +492,8 @@ extern "C" int ukm_taxonomy_load(ukm_ctx *c, const uint32_t *child, const uint32
     if (c->tax_parent) (void)hipFree(c->tax_parent);
     if (c->tax_depth) (void)hipFree(c->tax_depth);
     if (c->tax_merged) (void)hipFree(c->tax_merged);
+    if (c->tax_rank) (void)hipFree(c->tax_rank);  // (the ranks name the nodes of the tables that go)
+    c->tax_rank = nullptr;
     if (c->tax_anc) (void)hipFree(c->tax_anc);
     if (c->tax_euler) (void)hipFree(c->tax_euler);
     if (c->tax_node_at) (void)hipFree(c->tax_node_at);
@@ -494,6 +554,107 @@ extern "C" int ukm_lca(ukm_ctx *ctx, const uint32_t *a, const uint32_t *b, uint6
         UKM_TRY(ukm_out_t(ctx, out, n, &o));
         hipLaunchKernelGGL(lca_bulk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                            ukm_taxdev(ctx), da, db, n, o);
+        UKM_HIP(hipGetLastError());
+        return UKM_OK;
+    }();
+    return ukm_finish(&s, rc);
+}
+
+// ---- ranks ------------------------------------------------------------------------------------------------------------
+extern "C" int ukm_taxonomy_set_ranks(ukm_ctx *c, const uint32_t *child, const uint8_t *rank_id, uint64_t n) {
+    if (!c || (n && (!child || !rank_id))) UKM_FAIL(UKM_ERR_INVALID, "ukm_taxonomy_set_ranks: NULL argument");
+    if (!c->tax_parent) UKM_FAIL(UKM_ERR_NO_TAXONOMY, "ukm_taxonomy_set_ranks: no taxonomy loaded");
+    UKM_HIP(hipSetDevice(c->device));
+    std::vector<u32> ch, P;
+    std::vector<u8> rk;
+    UKM_TRY(to_host(c, child, n, ch));
+    UKM_TRY(to_host(c, rank_id, n, rk));
+    const u64 size = c->tax_size;
+    UKM_TRY(to_host(c, (const u32 *)c->tax_parent, size, P));
+    std::vector<u8> R(size, 0);
+    for (u64 i = 0; i < n; i++) {
+        if (ch[i] >= size || P[ch[i]] == 0)
+            UKM_FAIL(UKM_ERR_INVALID, "ukm_taxonomy_set_ranks: taxid %u (entry %llu) is not a node of the loaded taxonomy", ch[i], (unsigned long long)i);
+        R[ch[i]] = rk[i];
+    }
+    // built beside the current column and swapped in: a failure leaves the context as it was
+    u8 *n_rank = nullptr;
+    UKM_HIP(hipMalloc((void **)&n_rank, size * sizeof(u8)));
+    const hipError_t e = hipMemcpy(n_rank, R.data(), size * sizeof(u8), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(n_rank);
+        UKM_HIP(e);
+    }
+    UKM_HIP(hipStreamSynchronize(c->stream));
+    if (c->tax_rank) (void)hipFree(c->tax_rank);
+    c->tax_rank = n_rank;
+    return UKM_OK;
+}
+
+extern "C" int ukm_rank_filter_plan(const ukm_rank_filter *f, uint8_t self_action[256], uint8_t walk_action[256]) {
+    if (!f || !self_action || !walk_action) UKM_FAIL(UKM_ERR_INVALID, "ukm_rank_filter_plan: NULL argument");
+    if (f->lower != 0 && f->higher != 0) UKM_FAIL(UKM_ERR_INVALID, "ukm_rank_filter_plan: lower and higher can't be given together");
+    if (f->n_equal < 0 || f->n_equal > 32) UKM_FAIL(UKM_ERR_INVALID, "ukm_rank_filter_plan: n_equal = %d out of range (0..32)", (int)f->n_equal);
+    self_action[0] = 0;  // no known rank: dropped, and never what ends a walk
+    walk_action[0] = 0;
+    for (int r = 1; r < 256; r++) {
+        const int32_t o = f->order[r];
+        walk_action[r] = o > 0 ? (o <= f->lower ? 1 : 2) : 0;
+        if (f->black[r]) { self_action[r] = 0; continue; }
+        if (f->no_rank[r] && f->discard_norank) {
+            if (!f->save_norank) { self_action[r] = 0; continue; }
+            if (f->lower != 0) { self_action[r] = 2; continue; }
+        }
+        bool among = false;
+        for (int e = 0; e < f->n_equal; e++) among |= f->equal[e] == o;
+        bool pass;
+        if (among) pass = true;
+        else if (f->lower != 0) pass = o < f->lower;
+        else if (f->higher != 0) pass = o > f->higher;
+        else pass = f->n_equal == 0;
+        self_action[r] = pass ? 1 : 0;
+    }
+    return UKM_OK;
+}
+
+int ukm_dev_rank_bitmap(ukm_ctx *c, const char *name, const ukm_rank_filter *f, u32 **bits) {
+    if (!c->tax_parent) UKM_FAIL(UKM_ERR_NO_TAXONOMY, "%s: no taxonomy loaded", name);
+    if (!c->tax_rank) UKM_FAIL(UKM_ERR_NO_TAXONOMY, "%s: the taxonomy has no ranks (ukm_taxonomy_set_ranks)", name);
+    u8 sa[256], wa[256];
+    UKM_TRY(ukm_rank_filter_plan(f, sa, wa));
+    RankPlan plan;
+    memcpy(plan.self_action, sa, 256);
+    memcpy(plan.walk_action, wa, 256);
+    const u32 size = c->tax_size;
+    // every wave of the grid writes its two words: the array is sized by the grid (eight words per workgroup)
+    const unsigned blocks = (unsigned)(((size_t)size + 255) / 256);
+    u32 *b = nullptr;
+    UKM_TRY(ws_alloc_t(c, (size_t)blocks * 8, &b));
+    hipLaunchKernelGGL(rank_keep_kernel, dim3(blocks), dim3(256), 0, c->stream, (const u32 *)c->tax_parent, (const u32 *)c->tax_merged,
+                       (const u8 *)c->tax_rank, size, plan, f->discard_root ? 1u : 0u, (u32)f->root_taxid, b);
+    UKM_HIP(hipGetLastError());
+    *bits = b;
+    return UKM_OK;
+}
+
+extern "C" int ukm_rank_pass(ukm_ctx *ctx, const ukm_rank_filter *f, const uint32_t *taxids, uint64_t n, uint8_t *out) {
+    if (!ctx || !f || (n && (!taxids || !out))) UKM_FAIL(UKM_ERR_INVALID, "ukm_rank_pass: NULL argument");
+    if (!ctx->tax_parent || !ctx->tax_rank) UKM_FAIL(UKM_ERR_NO_TAXONOMY, "ukm_rank_pass: no taxonomy with ranks loaded");
+    {
+        u8 sa[256], wa[256];
+        UKM_TRY(ukm_rank_filter_plan(f, sa, wa));
+    }
+    if (n == 0) return UKM_OK;
+    CallScope s;
+    UKM_TRY(ukm_begin(ctx, &s));
+    int rc = [&]() -> int {
+        const u32 *t = nullptr;
+        u8 *o = nullptr;
+        u32 *bits = nullptr;
+        UKM_TRY(ukm_in_t(ctx, taxids, n, &t));
+        UKM_TRY(ukm_out_t(ctx, out, n, &o));
+        UKM_TRY(ukm_dev_rank_bitmap(ctx, "ukm_rank_pass", f, &bits));
+        hipLaunchKernelGGL(rank_pass_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)bits, ctx->tax_size, t, n, o);
         UKM_HIP(hipGetLastError());
         return UKM_OK;
     }();

@@ -12,9 +12,11 @@
 //   map / uniqs (map.go, -x 0 -X 0, linear)  .unik files -> ukm_union -> per genome file ukm_map -> BED3 | FASTA
 //   grep / filter / sample (grep.go, filter.go, sample.go)  per input file ukm_grep | ukm_filter | ukm_sample: the kept records
 //          in input order with their own taxids; grep -s/-u/-d -> ukm_sort_* -> ukm_unique
+//   rfilter (rfilter.go)  nodes.dmp with ranks + rank file -> ukm_taxonomy_set_ranks; per input file ukm_rfilter
+//   tsplit  (tsplit.go)   the files' records with their taxids -> ukm_tsplit -> one .unik per taxid
 // CPU-only commands (no GPU needed): view, dump, num, info/stats, concat, head, encode, decode.
 // `count` keeps the window values on the device from encode to the final set (chunked, double-buffered upload).
-// Not implemented (SURVEY.md §2a out of scope): rfilter (needs rank names), tsplit (a sort by taxid), grep -m/-O/-S/--force,
+// Not implemented (SURVEY.md §2a out of scope): grep -m/-O/-S/--force, rfilter's built-in default rank list,
 // map -x/-X/--circular, autocompletion; count -S (syncmer sketch: third-party rule not reconstructable from the tree).
 #include <dirent.h>
 #include <getopt.h>
@@ -1411,6 +1413,319 @@ static int cmd_filter(int argc, char **argv) {  // filter.go:43-168
     return 0;
 }
 
+// =================================================================================================
+// rfilter / tsplit: the TaxId workflow's last two steps
+// =================================================================================================
+// nodes.dmp with its third column: the rank of every node, lower-cased (taxdump keeps them as they are; every use in
+// rfilter.go lower-cases first)
+struct TaxDump {
+    vector<u32> child, parent, mo, mn;
+    vector<string> rank;  // of child[i]; empty when the line has no third column
+};
+static string lower_trim(string s) {
+    size_t a = 0, b = s.size();
+    while (a < b && isspace((unsigned char)s[a])) a++;
+    while (b > a && isspace((unsigned char)s[b - 1])) b--;
+    s = s.substr(a, b - a);
+    for (auto &ch : s) ch = (char)tolower((unsigned char)ch);
+    return s;
+}
+static TaxDump read_taxdump_with_ranks(const Options &o) {
+    const string nodes = o.data_dir + "/nodes.dmp", merged = o.data_dir + "/merged.dmp";
+    if (!file_exists(nodes)) die("taxonomy file not found: %s (set --data-dir or UNIKMER_DB)", nodes.c_str());
+    info("loading Taxonomy from: %s", o.data_dir.c_str());
+    TaxDump d;
+    std::ifstream fh(nodes);
+    string line;
+    u32 a, b;
+    while (std::getline(fh, line)) {
+        if (!parse_two_ids(line, a, b)) continue;
+        d.child.push_back(a); d.parent.push_back(b);
+        string r;
+        size_t p1 = line.find('|'), p2 = p1 == string::npos ? p1 : line.find('|', p1 + 1);
+        if (p2 != string::npos) {
+            size_t p3 = line.find('|', p2 + 1);
+            r = lower_trim(line.substr(p2 + 1, p3 == string::npos ? string::npos : p3 - p2 - 1));
+        }
+        d.rank.push_back(r);
+    }
+    if (file_exists(merged)) {
+        std::ifstream mh(merged);
+        while (std::getline(mh, line)) if (parse_two_ids(line, a, b)) { d.mo.push_back(a); d.mn.push_back(b); }
+    }
+    info("%zu nodes loaded, %zu merged nodes loaded", d.child.size(), d.mo.size());
+    return d;
+}
+// the with-ranks variant of load_taxonomy: rank_ids numbers the rank strings 1..255
+static void upload_taxonomy_with_ranks(Gpu &g, const TaxDump &d, const std::map<string, int> &rank_ids) {
+    ck(ukm_taxonomy_load(g.c, d.child.data(), d.parent.data(), d.child.size(), d.mo.empty() ? nullptr : d.mo.data(),
+                         d.mn.empty() ? nullptr : d.mn.data(), d.mo.size()));
+    vector<uint8_t> ids(d.child.size(), 0);
+    for (size_t i = 0; i < ids.size(); i++)
+        if (!d.rank[i].empty()) ids[i] = (uint8_t)rank_ids.at(d.rank[i]);
+    ck(ukm_taxonomy_set_ranks(g.c, d.child.data(), ids.data(), ids.size()));
+}
+
+// readRankOrderFromFile (rfilter.go:522-580): lines in descending order, the LAST line gets order 1; "!" marks ranks without order
+struct RankOrder {
+    std::map<string, int> order;
+    std::set<string> noranks;
+};
+static RankOrder read_rank_order_file(const string &file) {
+    std::ifstream fh(file);
+    if (!fh) die("%s: read rank order list from '%s': %s", file.c_str(), file.c_str(), strerror(errno));
+    vector<vector<string>> ranks;
+    RankOrder ro;
+    string line;
+    while (std::getline(fh, line)) {
+        size_t a = 0, b = line.size();
+        while (a < b && isspace((unsigned char)line[a])) a++;
+        while (b > a && isspace((unsigned char)line[b - 1])) b--;
+        const string record = line.substr(a, b - a);
+        if (record.empty() || record[0] == '#') continue;
+        vector<string> items;
+        std::istringstream ss(record);
+        string item;
+        while (std::getline(ss, item, ',')) {
+            if (item.empty()) continue;
+            item = lower_trim(item);
+            if (item.empty()) continue;
+            if (item[0] == '!') ro.noranks.insert(item.substr(1));
+            else items.push_back(item);
+        }
+        if (!items.empty()) ranks.push_back(items);
+    }
+    if (ranks.empty()) die("%s: no ranks found in file: %s", file.c_str(), file.c_str());
+    int order = 1;
+    for (size_t i = ranks.size(); i-- > 0; order++)
+        for (auto &r : ranks[i]) {
+            if (ro.order.count(r)) die("%s: duplicated rank: %s", file.c_str(), r.c_str());
+            ro.order[r] = order;
+        }
+    return ro;
+}
+static RankOrder read_rank_order(const Options &o, const string &rank_file) {  // rfilter.go:582-609
+    if (!rank_file.empty()) {
+        info("read rank order from: %s", rank_file.c_str());
+        return read_rank_order_file(rank_file);
+    }
+    // (the reference writes its built-in list to <data-dir>/ranks.txt when that file is missing; this driver carries no list)
+    const string def = o.data_dir + "/ranks.txt";
+    if (!file_exists(def))
+        die("default rank file not found: %s; give the ordered ranks with -r/--rank-file (type \"unikmer rfilter --help\" for the format)", def.c_str());
+    info("read rank order from: %s", def.c_str());
+    return read_rank_order_file(def);
+}
+// names by order, descending; the names of one order alphabetically
+static vector<std::pair<int, string>> by_order_desc(const std::map<string, int> &m) {
+    vector<std::pair<int, string>> v;
+    for (auto &kv : m) v.emplace_back(kv.second, kv.first);
+    std::sort(v.begin(), v.end(), [](const std::pair<int, string> &x, const std::pair<int, string> &y) {
+        return x.first != y.first ? x.first > y.first : x.second < y.second;
+    });
+    return v;
+}
+
+static int cmd_rfilter(int argc, char **argv) {  // rfilter.go:66-341
+    Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'r', "rank-file", true}, {0, "list-order", false}, {0, "list-ranks", false},
+                                     {'N', "discard-noranks", false}, {'n', "save-predictable-norank", false}, {'B', "black-list", true},
+                                     {'R', "discard-root", false}, {0, "root-taxid", true}, {'L', "lower-than", true}, {'H', "higher-than", true},
+                                     {'E', "equal-to", true}});
+    if (a.has("help")) {
+        fprintf(stderr,
+                "unikmer rfilter: filter k-mers by taxonomic rank\n\n"
+                "  -o out prefix  -r rank file  --list-order  --list-ranks  -N discard ranks without order  -n keep predictable ones (with -L)\n"
+                "  -B black list of ranks  -R discard the root taxid (--root-taxid, default 1)  -L / -H / -E rank limits\n\n"
+                "Rank file: blank lines and lines starting with \"#\" are ignored; ranks in descending order, case ignored; ranks of the\n"
+                "same order in one line separated with commas; ranks without order carry the prefix \"!\".  Without -r the file\n"
+                "<data-dir>/ranks.txt is read.\n");
+        return 0;
+    }
+    Options o = get_options(a);
+    const bool list_order = a.has("list-order"), list_ranks = a.has("list-ranks");
+    vector<string> files;
+    if (!list_order && !list_ranks) files = get_files(a, o);
+    const string lower = lower_trim(a.str("lower-than")), higher = lower_trim(a.str("higher-than"));
+    vector<string> equals, black;
+    for (auto &e : a.list("equal-to")) equals.push_back(lower_trim(e));
+    for (auto &e : a.list("black-list")) if (!lower_trim(e).empty()) black.push_back(lower_trim(e));
+    bool discard_norank = a.has("discard-noranks");
+    const bool save_norank = a.has("save-predictable-norank"), discard_root = a.has("discard-root");
+    if (!higher.empty() && !lower.empty()) die("-H/--higher-than and -L/--lower-than can't be simultaneous given");
+    if (save_norank) {
+        discard_norank = true;
+        if (lower.empty()) die("flag -n/--save-predictable-norank only works along with -L/--lower-than");
+    }
+    RankOrder ro = read_rank_order(o, a.str("rank-file"));
+    if (list_order) {  // needs no taxonomy and no device
+        int pre = -1;
+        for (auto &p : by_order_desc(ro.order)) {
+            if (p.first == pre) printf(",%s", p.second.c_str());
+            else { if (pre != -1) printf("\n"); printf("%s", p.second.c_str()); pre = p.first; }
+        }
+        printf("\n");
+        return 0;
+    }
+    TaxDump dump = read_taxdump_with_ranks(o);
+    std::map<string, int> rank_ids;  // the taxonomy's rank strings, numbered 1.. in sorted order
+    for (auto &r : dump.rank) if (!r.empty()) rank_ids[r] = 0;
+    {
+        vector<string> undefined;
+        int id = 0;
+        for (auto &kv : rank_ids) {
+            kv.second = ++id;
+            if (!ro.order.count(kv.first) && !ro.noranks.count(kv.first)) undefined.push_back(kv.first);
+        }
+        if (!undefined.empty()) {
+            string joined;
+            for (auto &r : undefined) joined += (joined.empty() ? "" : ", ") + r;
+            die("rank order not defined in rank file: %s", joined.c_str());
+        }
+        if (id > 255) die("%d different ranks in %s/nodes.dmp; rank ids are one byte (at most 255)", id, o.data_dir.c_str());
+    }
+    if (list_ranks) {
+        std::map<string, int> m;
+        for (auto &kv : rank_ids) m[kv.first] = ro.order.count(kv.first) ? ro.order[kv.first] : 0;
+        for (auto &p : by_order_desc(m)) printf("%s\n", p.second.c_str());
+        return 0;
+    }
+    // newRankFilter (rfilter.go:371-436) in rank ids
+    ukm_rank_filter f;
+    memset(&f, 0, sizeof(f));
+    auto order_of = [&](const string &rank) -> int {  // getRankOrder
+        if (!ro.order.count(rank)) die("rank order not defined in rank file: %s", rank.c_str());
+        if (!rank_ids.count(rank)) die("rank order not found in taxonomy database: %s", rank.c_str());
+        return ro.order[rank];
+    };
+    for (auto &kv : rank_ids) {
+        if (ro.order.count(kv.first)) f.order[kv.second] = ro.order[kv.first];
+        if (ro.noranks.count(kv.first)) f.no_rank[kv.second] = 1;
+    }
+    for (auto &r : black) if (rank_ids.count(r)) f.black[rank_ids[r]] = 1;
+    if (!lower.empty()) f.lower = order_of(lower);
+    if (!higher.empty()) f.higher = order_of(higher);
+    {
+        std::set<int> oe;
+        for (auto &e : equals) oe.insert(order_of(e));
+        if (oe.size() > 32) die("more than 32 different rank orders given with -E/--equal-to");
+        for (int v : oe) f.equal[f.n_equal++] = v;
+    }
+    f.discard_norank = discard_norank; f.save_norank = save_norank; f.discard_root = discard_root;
+    f.root_taxid = (u32)a.num("root-taxid", 1);
+    // the inputs, all of them before a device is touched: every file needs taxid information (rfilter.go:260-278)
+    const string out_file = out_name(a.str("out-prefix", "-"));
+    vector<Loaded> ins;
+    u64 total = 0;
+    for (size_t i = 0; i < files.size(); i++) {
+        info("processing file (%zu/%zu): %s", i + 1, files.size(), files[i].c_str());
+        ins.push_back(load_unik(files[i], o));
+        if (i > 0) check_compat(ins[0].h, ins[i].h, files[i]);
+        if (!ins[i].has_taxid) die("taxid information not found: %s", files[i].c_str());
+        total += ins[i].codes.size();
+    }
+    vector<u64> codes;
+    vector<u32> taxids;
+    if (total) {
+        Gpu g(o.gpu);
+        upload_taxonomy_with_ranks(g, dump, rank_ids);
+        vector<u64> ok;
+        vector<u32> ot;
+        for (auto &L : ins) {
+            if (L.codes.empty()) continue;
+            ok.resize(L.codes.size());
+            const bool own = L.per_record();
+            if (own) ot.resize(L.codes.size());
+            u64 n = 0;
+            ck(ukm_rfilter(g.c, L.codes.data(), own ? L.taxids.data() : nullptr, L.file_taxid, L.codes.size(), &f, ok.data(),
+                           own ? ot.data() : nullptr, ok.size(), &n));
+            append_selected(L, true, ok, ot, n, codes, taxids);
+        }
+    }
+    // the output flag: the first input's | include-taxid; the taxid width follows that reader (rfilter.go:268-272)
+    write_following(out_file, o, ins[0].h, ins[0].h.flag | unik::UnikIncludeTaxID, codes.data(), taxids.data(), codes.size());
+    return 0;
+}
+
+static int cmd_tsplit(int argc, char **argv) {  // tsplit.go:58-300
+    Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'O', "out-dir", true}, {0, "force", false}});
+    Options o = get_options(a);
+    const string prefix = a.has("out-prefix") ? a.str("out-prefix") : string("tsplit");
+    if (prefix.empty() || prefix[0] == '.') die("-o/--out-prefix should not be empty or starting with \".\"");
+    vector<string> files = get_files(a, o);
+    string outdir = a.str("out-dir");
+    if (outdir.empty()) outdir = files[0] == "-" ? "stdin.tsplit" : files[0] + ".tsplit";
+    // the inputs (all of them before the directory and the device are touched): records are read with the taxid the
+    // reader hands out -- their own, the file's global one, or 0 -- also under -I, which only switches off the check that
+    // the files agree (tsplit.go:149,163,176)
+    Options oo = o;
+    oo.ignore_taxid = false;
+    vector<u64> codes;
+    vector<u32> taxids;
+    unik::Header h0;
+    bool has_taxid0 = false;
+    int taxid_bytes = 1;
+    for (size_t i = 0; i < files.size(); i++) {
+        info("processing file (%zu/%zu): %s", i + 1, files.size(), files[i].c_str());
+        Loaded L = load_unik(files[i], oo);
+        if (i == 0) {
+            h0 = L.h;
+            has_taxid0 = L.h.has_taxid_info();
+            if (!L.h.is_sorted()) die("input should be sorted: %s", files[i].c_str());
+            taxid_bytes = L.h.taxid_bytes;
+        } else {
+            check_compat(h0, L.h, files[i]);
+            if (!o.ignore_taxid && L.h.has_taxid_info() != has_taxid0)
+                die(L.h.has_taxid_info() ? "taxid information not found in previous files, but found in this: %s"
+                                         : "taxid information found in previous files, but missing in this: %s", files[i].c_str());
+            taxid_bytes = std::max(taxid_bytes, (int)L.h.taxid_bytes);
+        }
+        codes.insert(codes.end(), L.codes.begin(), L.codes.end());
+        if (L.per_record()) taxids.insert(taxids.end(), L.taxids.begin(), L.taxids.end());
+        else taxids.insert(taxids.end(), L.codes.size(), L.file_taxid);
+    }
+    {   // tsplit.go:92-110: an output directory that is not empty is emptied with --force, and only warned about without
+        char cwd[4096];
+        const string pwd = getcwd(cwd, sizeof cwd) ? cwd : "";
+        if (outdir != "./" && outdir != "." && outdir != pwd) {
+            if (dir_exists(outdir)) {
+                vector<string> names = list_dir(outdir);
+                if (!names.empty()) {
+                    if (a.has("force")) {
+                        for (auto &n : names) if (remove((outdir + "/" + n).c_str()) != 0) die("fail to remove %s/%s", outdir.c_str(), n.c_str());
+                    } else {
+                        warn("outdir not empty: %s, you can use --force to overwrite", outdir.c_str());
+                    }
+                }
+            } else {
+                prepare_dir(outdir, false, "out-dir");
+            }
+        }
+    }
+    const u64 n = codes.size();
+    if (n == 0) { warn("%d taxids loaded", 0); return 0; }
+    vector<u64> out(n), off;
+    vector<u32> gt;
+    {
+        Gpu g(o.gpu);
+        u64 groups = 0;
+        const int rc = ukm_tsplit(g.c, codes.data(), taxids.data(), n, nullptr, 0, nullptr, nullptr, 0, &groups);  // the size query
+        if (rc != UKM_ERR_CAPACITY) ck(rc);
+        gt.resize(groups); off.resize(groups + 1);
+        ck(ukm_tsplit(g.c, codes.data(), taxids.data(), n, out.data(), n, gt.data(), off.data(), groups, &groups));
+    }
+    info("%llu taxids belonging to %zu taxids loaded", (unsigned long long)n, gt.size());
+    u32 mode = unik::UnikSorted;
+    if (h0.is_canonical()) mode |= unik::UnikCanonical;
+    if (h0.is_hashed()) mode |= unik::UnikHashed;
+    const u32 max_taxid = taxid_bytes >= 4 ? 0xFFFFFFFFu : ((1u << (8 * taxid_bytes)) - 1);  // maxUint32N: follow the readers
+    for (size_t gi = 0; gi < gt.size(); gi++) {
+        const string file = outdir + "/" + prefix + ".taxid-" + std::to_string(gt[gi]) + ".k" + std::to_string(h0.k) + EXT;
+        write_unik(file, o, h0.k, mode, max_taxid, gt[gi], nullptr, out.data() + off[gi], nullptr, off[gi + 1] - off[gi]);
+    }
+    info("%llu taxids belonging to %zu taxids saved to dir: %s", (unsigned long long)n, gt.size(), outdir.c_str());
+    return 0;
+}
+
 static void hash_kmers_on_device(Gpu &g, const vector<string> &kmers, int k, bool canonical, vector<u64> &out);
 
 // util.go:173-245 extendDegenerateSeq: every sequence a degenerate one stands for, in the reference's order
@@ -1984,7 +2299,7 @@ static void usage() {
     fprintf(stderr,
             "unikmer (HIP) - k-mer set operations on AMD MI355X behind the unikmer command line\n\n"
             "Usage: unikmer <command> [flags] [files]\n\n"
-            "GPU commands : count sort split merge union inter diff common locate map(uniqs) grep filter sample\n"
+            "GPU commands : count sort split merge union inter diff common locate map(uniqs) grep filter sample rfilter tsplit\n"
             "CPU commands : view dump num info(stats) concat head encode decode version\n"
             "Global flags : -j --verbose -C --compression-level -c -i -I --max-taxid --data-dir --gpu\n");
 }
@@ -2007,6 +2322,8 @@ int main(int argc, char **argv) {
         if (cmd == "grep") return cmd_grep(argc, argv);
         if (cmd == "filter") return cmd_filter(argc, argv);
         if (cmd == "sample") return cmd_sample(argc, argv);
+        if (cmd == "rfilter") return cmd_rfilter(argc, argv);
+        if (cmd == "tsplit") return cmd_tsplit(argc, argv);
         if (cmd == "view") return cmd_view(argc, argv);
         if (cmd == "dump") return cmd_dump(argc, argv);
         if (cmd == "num") return cmd_num(argc, argv);

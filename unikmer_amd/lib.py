@@ -38,7 +38,38 @@ SYMBOLS = [
     "ukm_ctx_set_option", "ukm_ctx_unset_option", "ukm_ctx_get_option", "ukm_ctx_get_stat",
     "ukm_setop2_ft", "ukm_union_ft", "ukm_inter_ft", "ukm_diff_ft", "ukm_common_ft", "ukm_merge_k_ft",
     "ukm_locate", "ukm_map", "ukm_grep", "ukm_filter", "ukm_sample",
+    "ukm_taxonomy_set_ranks", "ukm_rank_filter_plan", "ukm_rank_pass", "ukm_rfilter", "ukm_tsplit",
 ]
+
+
+class RankFilter(C.Structure):
+    """ukm_rank_filter (include/unikmer_hip.h): a rank filter stated in rank ids and orders.  RankFilter.make builds one
+    from plain Python values."""
+    _fields_ = [("order", C.c_int32 * 256), ("no_rank", C.c_uint8 * 256), ("black", C.c_uint8 * 256),
+                ("lower", C.c_int32), ("higher", C.c_int32), ("equal", C.c_int32 * 32), ("n_equal", C.c_int32),
+                ("discard_norank", C.c_uint8), ("save_norank", C.c_uint8), ("discard_root", C.c_uint8),
+                ("root_taxid", C.c_uint32)]
+
+    @classmethod
+    def make(cls, order=None, no_rank=(), black=(), lower=0, higher=0, equal=(), discard_norank=False, save_norank=False,
+             discard_root=False, root_taxid=1):
+        """order: {rank id: order > 0}; no_rank / black: rank ids; lower / higher / equal: ORDERS (0 = not given)"""
+        f = cls()
+        for r, o in (order or {}).items():
+            f.order[int(r)] = int(o)
+        for r in no_rank:
+            f.no_rank[int(r)] = 1
+        for r in black:
+            f.black[int(r)] = 1
+        f.lower, f.higher = int(lower), int(higher)
+        equal = list(equal)
+        for i, o in enumerate(equal[:32]):
+            f.equal[i] = int(o)
+        f.n_equal = len(equal)          # (more than 32: the library refuses it)
+        f.discard_norank, f.save_norank, f.discard_root = int(bool(discard_norank)), int(bool(save_norank)), int(bool(discard_root))
+        f.root_taxid = int(root_taxid)
+        return f
+
 
 
 class UkmError(RuntimeError):
@@ -134,6 +165,11 @@ def load():
     L.ukm_grep.argtypes = [vp, vp, vp, u32, u64, i32, vp, vp, u64, u32, vp, vp, u64, pu64]
     L.ukm_filter.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, i32, u32, vp, vp, u64, pu64]
     L.ukm_sample.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, u64, pu64]
+    L.ukm_taxonomy_set_ranks.argtypes = [vp, vp, vp, u64]
+    L.ukm_rank_filter_plan.argtypes = [vp, vp, vp]
+    L.ukm_rank_pass.argtypes = [vp, vp, vp, u64, vp]
+    L.ukm_rfilter.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, pu64]
+    L.ukm_tsplit.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, pu64]
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -358,6 +394,29 @@ class Context:
         _check(self.L.ukm_lca(self.h, pa, pb, n, po))
         return out[:n]
 
+    def taxonomy_set_ranks(self, child, rank_id):
+        """rank_id[i] in 1..255 = the rank of child[i] (the caller numbers the rank names), 0 = no known rank"""
+        pc, n, k1 = _ptr(child, np.uint32)
+        pr, n2, k2 = _ptr(rank_id, np.uint8)
+        assert n == n2
+        _check(self.L.ukm_taxonomy_set_ranks(self.h, pc, pr, n))
+
+    @staticmethod
+    def rank_filter_plan(f):
+        """the decision of a RankFilter per rank id, as the pure host function the device pass uses: (self_action, walk_action),
+        256 bytes each (include/unikmer_hip.h: ukm_rank_filter_plan)"""
+        sa, wa = np.zeros(256, dtype=np.uint8), np.zeros(256, dtype=np.uint8)
+        _check(load().ukm_rank_filter_plan(C.addressof(f), sa.ctypes.data, wa.ctypes.data))
+        return sa, wa
+
+    def rank_pass(self, f, taxids):
+        """1 where a record with that taxid passes the RankFilter, else 0 (rfilter.go:438-520)"""
+        pt, n, k1 = _ptr(taxids, np.uint32)
+        out = _empty_like_kind(taxids, n, np.uint8)
+        po, _, _ = _ptr(out, np.uint8)
+        _check(self.L.ukm_rank_pass(self.h, C.addressof(f), pt, n, po))
+        return out[:n]
+
     # ---- encode / hash ----
     def _windows(self, fn, bases, rec_off, k, canonical, circular, max_hash, out):
         pb, nb, k1 = _ptr(bases, np.uint8)
@@ -519,6 +578,36 @@ class Context:
         return self._select(lambda pk, pt, n, po, pot, cap, m: self.L.ukm_sample(self.h, pk, pt, n, start, window, po, pot, cap, m),
                             keys, taxids, (lambda n: (n - start) // window + 1 if start >= 1 and window >= 1 and n >= start else 0),
                             out, out_taxids)
+
+    def rfilter(self, keys, f, taxids=None, out=None, out_taxids=None):
+        """`unikmer rfilter` (rfilter.go:280-304): the records whose taxid passes the RankFilter `f`, in input order, each with
+        its own taxid.  taxids as an int: the file's one taxid (a copy or an empty result)."""
+        ft = int(taxids) if _is_file_taxid(taxids) else 0
+        return self._select(lambda pk, pt, n, po, pot, cap, m: self.L.ukm_rfilter(self.h, pk, pt, ft, n, C.addressof(f), po, pot, cap, m),
+                            keys, taxids, None, out, out_taxids)
+
+    def tsplit(self, keys, taxids, out=None, group_taxids=None, group_off=None):
+        """`unikmer tsplit` (tsplit.go:112-192): the records grouped by taxid, groups ascending, a group's codes in input
+        order.  Returns (out_keys, group_taxids, group_off): group g is out_keys[group_off[g]:group_off[g + 1]].  Without
+        the group arrays the number of groups is asked for first (the size query)."""
+        pk, n, k1 = _ptr(keys, np.uint64)
+        pt, nt, k2 = _ptr(taxids, np.uint32)
+        assert taxids is None or nt == n
+        g = C.c_uint64()
+        if group_taxids is None or group_off is None:
+            rc = self.L.ukm_tsplit(self.h, pk, pt, n, None, 0, None, None, 0, C.byref(g))
+            if rc != ERR_CAPACITY:
+                _check(rc)
+            group_taxids = _empty_like_kind(keys, g.value, np.uint32)
+            group_off = _empty_like_kind(keys, g.value + 1, np.uint64)
+        if out is None:
+            out = _empty_like_kind(keys, n, np.uint64)
+        po, cap, _ = _ptr(out, np.uint64)
+        pg, gcap, _ = _ptr(group_taxids, np.uint32)
+        pf, fcap, _ = _ptr(group_off, np.uint64)
+        # group_off holds one entry more than group_taxids: the capacity is what both arrays take
+        _check(self.L.ukm_tsplit(self.h, pk, pt, n, po, cap if n else 0, pg, pf, min(gcap, max(fcap, 1) - 1), C.byref(g)), g.value)
+        return out[:n], group_taxids[: g.value], group_off[: g.value + 1 if n else 0]
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
