@@ -161,7 +161,11 @@ int ukm_last_route(ukm_ctx *ctx);
  *      an attempt that declines in front of its pass shows 0 and not an earlier call's word): 1 PU_FLAG_UNSORTED a file is not sorted, 2
  *      PU_FLAG_OVERFLOW the list of records the base set lacks outgrew its estimated size (stores are guarded), 4
  *      PU_FLAG_TAXID a taxid outside the loaded taxonomy, 8 PU_FLAG_RAW a record no table could take.  Any bit makes the
- *      route decline without having written the output, and the general merge answers the call. */
+ *      route decline without having written the output, and the general merge answers the call.
+ *      "setop_part_hits" = ukm_setop2 / ukm_setop2_ft calls of this context that took their merge-path table from the call
+ *      before them on the same two device buffers (after verifying it against the buffers as they are now),
+ *      "setop_part_stale" = such calls whose table failed the verification, so that the search ran after all (after two in
+ *      a row the context stops trying).  See ukm_setop2. */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);
@@ -368,7 +372,13 @@ int ukm_merge_k(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *const
                 uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
 
 /* ---- 2-way set operation on two SORTED streams — the device hot path that the n-way
- *      entries below are folded from, and what bench.py measures. */
+ *      entries below are folded from, and what bench.py measures.
+ *      Consecutive calls on the SAME two device buffers (same pointers, same sizes: union, then inter, then diff of one
+ *      pair) share one internal partition table: the context keeps the most recent one and the next call verifies it
+ *      against the buffers as they are now instead of computing it again; a table that no longer fits (the buffers were
+ *      rewritten in place) is computed anew.  Results never depend on this cache, only time does.  Host arrays, the n-way
+ *      entries and inputs of fewer than ~2.5e6 records in total never use it; statistics "setop_part_hits" /
+ *      "setop_part_stale" (ukm_ctx_get_stat). */
 int ukm_setop2(ukm_ctx *ctx, int op, const uint64_t *a_keys, const uint32_t *a_taxids,
                uint64_t na, const uint64_t *b_keys, const uint32_t *b_taxids, uint64_t nb,
                uint32_t flags, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap,

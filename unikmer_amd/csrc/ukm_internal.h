@@ -164,6 +164,24 @@ struct ukm_ctx {
     u64 stat_punion_attempts = 0;  // base sets the last probe union / counting probes built (2: the retry with 4 x the files ran)
     u64 stat_punion_flags = 0;     // the flag word (ctl[1], PU_FLAG_*) the most recent probe pass of this context left
     u64 stat_count_window_retries = 0;  // ukm_count calls that repeated the window pass: its estimated buffer was too small
+    u64 stat_setop_part_hits = 0;   // 2-way set operations that took their merge-path table from the partition cache (verified, see below)
+    u64 stat_setop_part_stale = 0;  // ... whose cached table failed the verification: the partition ran after all
+
+    // Partition cache of the public 2-way set operation (ukm_setops.hip: run_setop_pass).  The merge-path table depends on
+    // (A, B, |A|, |B|, tile size) only -- union, inter and diff of one pair share it -- so the context keeps the table of the
+    // most recent call in ONE slot of device memory of its own (never the arena: that is poisoned by tests and reused by
+    // every call) and the next call on the same key VERIFIES it against the inputs as they are now instead of searching
+    // again.  buf[0] = the verification's stale word (zero whenever `valid`), buf[PC_HEAD ...] = the table.
+    struct PartCache {
+        static constexpr size_t PC_HEAD = 8;  // u64 words in front of the table: a 64-byte line
+        u64 *buf = nullptr;
+        size_t cap_words = 0;
+        const u64 *a = nullptr, *b = nullptr;
+        u64 na = 0, nb = 0, tile_items = 0;
+        bool valid = false;
+        int stale_run = 0;  // stale hits in a row
+        bool off = false;   // two in a row (a caller that refills fixed buffers with same-sized batches): no more attempts
+    } part_cache;
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device
     bool setop_force_ticket = false;  // = ticket_latched || option "force_ticket"
@@ -354,8 +372,11 @@ int ukm_dev_fill_u32_from(ukm_ctx *c, u32 *dst, u64 n, u32 value, const u32 *val
 // record per code -- the caller is in the middle of an n-file fold (diff.go:437: mc1 = mc2 keeps every record; the map of
 // diff.go:449-453 only shapes the final result) and collapses once at the end
 #define UKM_F_INTERNAL_KEEP_DUPS 0x10000u
+// internal flag of ukm_dev_setop2_ct, set by the public 2-way entry alone: both key streams are the CALLER's device memory
+// (not arena copies, not an n-way route's intermediate), so the call may use the context's partition cache
+#define UKM_F_INTERNAL_PART_CACHE 0x20000u
 // flag bits of the set-op result word [1]
-enum { UKM_SETOP_FLAG_DUP = 1, UKM_SETOP_FLAG_UNSORTED = 2, UKM_SETOP_FLAG_TIMEOUT = 4 };
+enum { UKM_SETOP_FLAG_DUP = 1, UKM_SETOP_FLAG_UNSORTED = 2, UKM_SETOP_FLAG_TIMEOUT = 4, UKM_SETOP_FLAG_STALE = 8 };
 int ukm_dev_sort(ukm_ctx *c, u64 *keys, u32 *vals, u64 n, int key_bits);
 // the same with the first scatter pass's digit histogram already counted by the producer of the keys (ukm_count)
 int ukm_dev_sort_hist(ukm_ctx *c, u64 *keys, u32 *vals, u64 n, int key_bits, const u64 *first_hist, int first_shift);

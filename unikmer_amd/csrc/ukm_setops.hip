@@ -24,7 +24,9 @@
 
 namespace {
 
-enum { FLAG_DUP = 1, FLAG_UNSORTED = 2, FLAG_TIMEOUT = 4 };
+// FLAG_STALE: the launch ran on a merge-path table taken from the context's partition cache and the verification found a
+// boundary that does not hold for the inputs as they are now (setop_partition_verify_kernel): no tile has run
+enum { FLAG_DUP = 1, FLAG_UNSORTED = 2, FLAG_TIMEOUT = 4, FLAG_STALE = 8 };
 
 #ifndef SETOP_NT
 #define SETOP_NT 512
@@ -66,8 +68,14 @@ struct SetopArgs {
     // setop_taxid_fix_kernel settles them behind the launch; fix_cnt[tile] = how many (every tile writes it).  nullptr: none.
     uint4 *fix;
     u32 *fix_cnt;
+    // the stale word of the context's partition cache when `mp` is the cached table (ukm_ctx::PartCache), else nullptr.  Non-zero:
+    // the table failed its verification -- NO kernel of the launch may take an address from it.
+    const u64 *stale;
 };
 constexpr u32 FIX_SLOTS = 16;
+
+// (workgroup-uniform: one scalar load, in front of every read of p.mp)
+__device__ __forceinline__ bool setop_table_stale(const SetopArgs &p) { return p.stale != nullptr && sload_u64(p.stale) != 0; }
 
 // the actual sizes of a chained call (workgroup-uniform: one scalar load)
 __device__ __forceinline__ void setop_resolve_sizes(SetopArgs &p, u64 tile_items) {
@@ -250,6 +258,7 @@ __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p,
     // status lines of this segment's tiles; the control words in front of them
     if (tid < PART_COARSE && c0 + (u64)tid < p.ntiles) p.status[(c0 + (u64)tid) * LB_STRIDE] = 0;
     if (blockIdx.x == 0 && tid < (int)nclear) p.result[tid] = 0;
+    if (blockIdx.x == 0 && tid == 0 && p.stale) *const_cast<u64 *>(p.stale) = 0;  // a fresh table: whatever a verification said about the old one is void
     if (wave < 2) {
         const u64 t = wave == 0 ? c0 : c1;
         u64 diag = t * (u64)tile_items;
@@ -326,6 +335,43 @@ __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p,
         if (le) lo = mid + 1; else hi = mid;
     }
     p.mp[t] = lo;
+}
+
+// A hit of the partition cache: the table in p.mp was computed by the kernel above for the same (a, b, na, nb, tile_items),
+// but the buffers may have been rewritten since.  Searching again costs ~17 dependent round trips; CHECKING costs one:
+// the split a of diagonal d (b = d - a) is the merge path's if and only if A[a-1] <= B[b] and B[b-1] < A[a] (A before B on
+// ties, as in the searches above; each half holds trivially at an end of its input) -- four keys per boundary, all in
+// flight together.  The table may hold anything, so a split is checked against its legal range BEFORE a key is read, and
+// against its left neighbour's so that no tile is larger than the LDS it is staged in.  One thread per boundary; thread t
+// also clears tile t's status line, block 0 the control words (what the fused kernel does on a miss).  A bad boundary sets
+// the cache's stale word -- a word of its own: an OR into the control words would race with their clearing -- and every
+// kernel of the launch behind this one returns at its top (setop_table_stale).
+__global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p, int tile_items, u32 nclear) {
+    const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < nclear) p.result[threadIdx.x] = 0;
+    if (t < p.ntiles) p.status[t * LB_STRIDE] = 0;
+    if (t > p.ntiles) return;
+    const u64 N = p.na + p.nb;
+    u64 d = t * (u64)tile_items;
+    if (d > N) d = N;
+    const u64 a = p.mp[t];
+    const u64 lo = d > p.nb ? d - p.nb : 0, hi = d < p.na ? d : p.na;
+    bool good = a >= lo && a <= hi;
+    if (good && t > 0) {
+        // the tile in front of this boundary: 0 <= its A items <= its items (<= tile_items), which leaves its B items >= 0 too
+        const u64 dp = (t - 1) * (u64)tile_items;  // (< N: t <= ntiles)
+        const u64 ap = p.mp[t - 1];
+        good = a >= ap && a - ap <= d - dp;
+    }
+    if (good) {
+        const u64 b = d - a;  // <= nb by a >= lo
+        // (both loads of a test are issued whatever the other says: clamped, harmless indices where a half holds trivially)
+        const bool t1 = a != 0 && b != p.nb, t2 = b != 0 && a != p.na;
+        const u64 a1 = p.a[t1 ? a - 1 : 0], b1 = p.b[t1 ? b : 0];
+        const u64 b2 = p.b[t2 ? b - 1 : 0], a2 = p.a[t2 ? a : 0];
+        good = (!t1 || a1 <= b1) && (!t2 || b2 < a2);
+    }
+    if (!good) *const_cast<u64 *>(p.stale) = 1;  // (every writer writes the same value)
 }
 
 // UKM_OP_MERGE_INTERNAL (ukm_internal.h): plain 2-way MERGE of two non-decreasing streams, every record
@@ -517,9 +563,16 @@ __device__ __forceinline__ bool tile_is_fast(const SetopArgs &p, const TileGeom 
 // The same tile, global memory -> LDS without a register round trip (gfx950 LDS-DMA, `global_load_lds_dwordx4`): the
 // LDS image is lane-linear (wave-uniform base + 16 bytes per lane), which is exactly the staging layout above; the
 // source address is per lane.  Saves the 40 staging VGPRs and the ds_write_b128 pass of the tile.
+// SETOP_DMA_NT: the cache policy of these loads (the `aux` operand of the builtin; on gfx950 bit 1 = nt, "non-temporal":
+// the lines are the first to leave the caches).  0 = the default policy, 1 = nt.  An experiment switch like SETOP_WAVES:
+// the measurements behind the default are in profiles/part_reuse_notes.md.
+#ifndef SETOP_DMA_NT
+#define SETOP_DMA_NT 0
+#endif
 template <int NTH, int VT>
 __device__ __forceinline__ void tile_dma_fast(const SetopArgs &p, const TileGeom &g, int tid, u64 *s_keys) {
     constexpr int NP = TilePairs<NTH, VT>::NP;
+    constexpr int AUX = SETOP_DMA_NT ? 2 : 0;
     constexpr int SLOTS = NTH * VT + 8;
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(1))) const void glb_void;
@@ -532,9 +585,9 @@ __device__ __forceinline__ void tile_dma_fast(const SetopArgs &p, const TileGeom
         const u64 *src = (s0 < g.split ? pa : pb) + s0;
         u64 *dst = s_keys + 2 * (wbase + j * NTH);  // wave-uniform; lane l lands 16 l bytes behind it
         if (2 * (NTH - 1 + j * NTH) + 1 >= SLOTS) {  // last round only (compile time): lanes beyond the tile stay off
-            if (s0 < SLOTS) __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)dst, 16, 0, 0);
+            if (s0 < SLOTS) __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)dst, 16, 0, AUX);
         } else {
-            __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)dst, 16, 0, AUX);
         }
     }
 }
@@ -954,6 +1007,7 @@ __global__ __launch_bounds__(GATHER_NT) void setop_taxid_gather_kernel(SetopArgs
     setop_resolve_sizes(p, (u64)TILE);
     const u64 tile = blockIdx.x;
     if (tile >= p.ntiles) return;
+    if (setop_table_stale(p)) return;  // (no tile has run: the host partitions and launches again)
     if (sload_u64(&p.result[1]) & FLAG_TIMEOUT) return;  // (the host runs the pass again: the status words are incomplete)
     u64 base, end;
     if (OP == UKM_OP_MERGE_INTERNAL) {
@@ -1042,6 +1096,7 @@ __global__ __launch_bounds__(256) void setop_taxid_fix_kernel(SetopArgs p) {
     const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 tile = g / FIX_SLOTS;
     if (tile >= p.ntiles) return;
+    if (setop_table_stale(p)) return;  // (no tile has run: nobody has written fix_cnt)
     if (sload_u64(&p.result[1]) & FLAG_TIMEOUT) return;  // (the host runs the pass again: not every tile has written its count)
     if ((u32)(g % FIX_SLOTS) >= p.fix_cnt[tile]) return;
     const uint4 e = p.fix[g];
@@ -1109,7 +1164,11 @@ void setop_tile_kernel(SetopArgs p) {
     const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     PH(0);
     setop_resolve_sizes(p, (u64)TILE);
-    if (tile >= p.ntiles) return;  // chained call: the launch covers the upper bound of |A|
+    // chained call: the launch covers the upper bound of |A|.  A cached partition that failed its verification: EVERY
+    // workgroup of the launch leaves here -- nothing loaded, published or stored, nobody waits in a look-back.  (Nothing but
+    // the return: a store on this way out, even one thread's, costs the plain instantiations 14 spilled registers;
+    // setop_stale_report_kernel tells the host.)
+    if (tile >= p.ntiles || setop_table_stale(p)) return;
     const TileGeom g = tile_geom<NTH, VT>(p, tile);
     u32 bad = 0;
     bool fast = false;  // workgroup-uniform
@@ -1285,6 +1344,11 @@ __global__ void lower_bound_kernel(const u64 *k, u64 n, const u64 *q, int nq, u6
     out[i] = lo;
 }
 
+// behind the kernels of a launch that works on the cached table: the verdict of its verification, where the host reads the flags
+__global__ void setop_stale_report_kernel(SetopArgs p) {
+    if (setop_table_stale(p)) p.result[1] = FLAG_STALE;  // (no tile has run: there are no other flags)
+}
+
 template <int OP, bool TAX, bool RANK, int NTH, int VT, bool CT = false, bool DEFER = false>
 void launch_tile(const SetopArgs &p, hipStream_t st, bool ticket) {
     if (CT) hipLaunchKernelGGL(setop_ct_kernel, dim3(1), dim3(1), 0, st, p, OP);
@@ -1325,9 +1389,11 @@ constexpr int VT_RANK = 12;  // ranks ride along (the multiset re-run), with or 
 
 // One pass of the tiled set operation.  result_host[0] = total, [1] = flags.
 // (cta, ctb): the file taxid of a stream whose ta / tb is null (SetopArgs); tax && !ta && !tb = the CT instantiation
+// may_cache: a and b are the caller's own device buffers (the public 2-way entry): the pass may take its merge-path table
+// from the context's partition cache, verified, and leave its own there.  Results never depend on the cache, only time does.
 int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *ra, u64 na,
                    const u64 *b, const u32 *tb, const u32 *rb, u64 nb, bool tax, u32 flags,
-                   u64 *out, u32 *tout, u64 out_cap, u64 result_host[2], u32 cta = 0, u32 ctb = 0) {
+                   u64 *out, u32 *tout, u64 out_cap, u64 result_host[2], u32 cta = 0, u32 ctb = 0, bool may_cache = false) {
     const bool rank = ra != nullptr;
     bool ct = tax && !ta && !tb;
     // per-record taxids on plain sets: EITHER the taxid instantiation (on a taxonomy with one-byte clade codes its DEFER
@@ -1377,7 +1443,40 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     // The partition points (they survive a repeated launch).  A plain call takes the fused kernel, which also zeroes
     // the control block for the first attempt.
     const bool fused = !ukm_env_is(c, "UKM_SETOP_FUSED_PART", '0') && p.ntiles >= 4 * PART_COARSE;  // (developer knob)
-    if (fused) {
+    // The partition cache (ukm_ctx::PartCache): only where the fused kernel would run -- below 4 * PART_COARSE tiles the
+    // partition is a 12 us kernel --, never with ranks (the multiset re-run), never on a chained link (sizes on the device:
+    // another entry point).  UKM_SETOP_PART_REUSE=0 (developer knob) turns it off.
+    ukm_ctx::PartCache &pc = c->part_cache;
+    bool cache = may_cache && fused && !rank && na && nb && !pc.off && !ukm_env_is(c, "UKM_SETOP_PART_REUSE", '0');
+    bool hit = false;
+    if (cache) {
+        const size_t need = ukm_ctx::PartCache::PC_HEAD + (size_t)p.ntiles + 1;
+        if (pc.cap_words < need) {  // grown on demand; the slot's table goes with the old buffer
+            if (pc.buf) (void)hipFree(pc.buf);
+            pc.buf = nullptr;
+            pc.cap_words = 0;
+            pc.valid = false;
+            void *nb_ = nullptr;
+            if (hipMalloc(&nb_, need * sizeof(u64)) == hipSuccess) {
+                pc.buf = (u64 *)nb_;
+                pc.cap_words = need;
+            } else {
+                (void)hipGetLastError();  // no room for a cache: the call goes on without one
+                cache = false;
+            }
+        }
+    }
+    if (cache) {
+        hit = pc.valid && pc.a == a && pc.b == b && pc.na == na && pc.nb == nb && pc.tile_items == tile_items;
+        pc.valid = false;  // until this pass has come back: an error on the way leaves no key behind
+        p.stale = pc.buf;
+        p.mp = pc.buf + ukm_ctx::PartCache::PC_HEAD;
+    }
+    if (hit) {
+        const unsigned vblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
+        hipLaunchKernelGGL(setop_partition_verify_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
+        UKM_HIP(hipGetLastError());
+    } else if (fused) {
         const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
         if (rank) hipLaunchKernelGGL((setop_partition_fused_kernel<true>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
         else hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
@@ -1399,7 +1498,7 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     }
     // (the bracket holds the tile kernel with its CT / fix / gather kernels, not the partition)
     const LbLaunch how = {"setop", "set-op kernel", FLAG_TIMEOUT, true, false, fused};
-    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+    const auto launch_tiles = [&](bool ticket) {
         if (rank) {
             if (tax) launch_op<true, true, NTS, VT_RANK>(op, p, c->stream, ticket);
             else if (ct) launch_op<false, true, NTS, VT_RANK, true>(op, p, c->stream, ticket);
@@ -1412,8 +1511,30 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
             else if (ct) launch_op<false, false, NTS, VT_PLAIN, true>(op, p, c->stream, ticket);
             else launch_op<false, false, NTS, VT_PLAIN>(op, p, c->stream, ticket);
         }
+        if (p.stale) hipLaunchKernelGGL(setop_stale_report_kernel, dim3(1), dim3(1), 0, c->stream, p);
         return UKM_OK;
-    }, result_host));
+    };
+    UKM_TRY(ukm_lb_launch(c, blk, how, launch_tiles, result_host));
+    if (hit) {
+        if (result_host[1] & FLAG_STALE) {
+            // The buffers were rewritten under the key.  No tile has run (the other flags of that pass mean nothing): the
+            // search after all -- its kernel clears the stale word and the control block -- and the launch again, once.
+            c->stat_setop_part_stale++;
+            if (++pc.stale_run >= 2) pc.off = true;
+            const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
+            hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
+            UKM_HIP(hipGetLastError());
+            UKM_TRY(ukm_lb_launch(c, blk, how, launch_tiles, result_host));
+        } else {
+            c->stat_setop_part_hits++;
+            pc.stale_run = 0;
+        }
+    }
+    if (result_host[1] & FLAG_STALE) UKM_FAIL(UKM_ERR_HIP, "setop: a fresh partition table failed its verification");
+    if (cache) {  // the table in the slot belongs to this pass's inputs as they were a moment ago
+        pc.a = a; pc.b = b; pc.na = na; pc.nb = nb; pc.tile_items = tile_items;
+        pc.valid = true;
+    }
 #ifdef UKM_PROFILE_PHASES
     {
         std::vector<u64> h((size_t)p.ntiles * 8);
@@ -1509,9 +1630,12 @@ int ukm_dev_setop2_ct(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u32 cta, 
     if (na + nb == 0) return UKM_OK;
     if (na + nb >= (1ull << 61)) UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2: input too large");
 
+    // (the partition cache serves this first pass alone: the re-runs below work on arena copies or with ranks)
+    const bool may_cache = (flags & UKM_F_INTERNAL_PART_CACHE) != 0 && op != UKM_OP_MERGE_INTERNAL;
+    flags &= ~UKM_F_INTERNAL_PART_CACHE;
     u64 res[2] = {0, 0};
     UKM_TRY(run_setop_pass(c, op, a, ta, nullptr, na, b, tb, nullptr, nb, tax, flags, out, tout,
-                           out_cap, res, cta, ctb));
+                           out_cap, res, cta, ctb, may_cache));
     if (res[1] & FLAG_UNSORTED) UKM_FAIL(UKM_ERR_UNSORTED, "ukm_setop2: an input stream is not sorted");
     if ((res[1] & FLAG_DUP) && op != UKM_OP_MERGE_INTERNAL) {
         // multiset inputs: redo with the exact reference semantics
@@ -1594,7 +1718,10 @@ extern "C" int ukm_setop2_ft(ukm_ctx *ctx, int op, const uint64_t *a_keys, const
         else UKM_TRY(ukm_out_t(ctx, out_taxids, out_cap, &tout));
         // (an empty stream's per-record pointer may be null: its file taxid plays no part then)
         const u32 cta = ta ? 0u : a_file_taxid, ctb = tb ? 0u : b_file_taxid;
-        int r = ukm_dev_setop2_ct(ctx, op, a, ta, cta, na, b, tb, ctb, nb, flags & (UKM_F_MIX_TAXID | UKM_F_CMP_TAXID), out, tout, out_cap, n_out);
+        // both key streams are the caller's device memory (ukm_in_t hands a device pointer back as it is; a host array
+        // becomes an arena copy, whose address the next call reuses with other data): the call may use the partition cache
+        const u32 cacheable = (s.top && na && nb && a == a_keys && b == b_keys) ? UKM_F_INTERNAL_PART_CACHE : 0u;
+        int r = ukm_dev_setop2_ct(ctx, op, a, ta, cta, na, b, tb, ctb, nb, (flags & (UKM_F_MIX_TAXID | UKM_F_CMP_TAXID)) | cacheable, out, tout, out_cap, n_out);
         u64 n = (r == UKM_OK) ? *n_out : 0;
         ukm_out_resize(ctx, out_keys, n * sizeof(u64));
         if (out_taxids) ukm_out_resize(ctx, out_taxids, n * sizeof(u32));
