@@ -165,7 +165,11 @@ int ukm_last_route(ukm_ctx *ctx);
  *      "setop_part_hits" = ukm_setop2 / ukm_setop2_ft calls of this context that took their merge-path table from the call
  *      before them on the same two device buffers (after verifying it against the buffers as they are now),
  *      "setop_part_stale" = such calls whose table failed the verification, so that the search ran after all (after two in
- *      a row the context stops trying).  See ukm_setop2. */
+ *      a row the context stops trying),
+ *      "setop_offs_hits" = of those hits, calls on plain codes (no taxids) whose pass also took the output offsets of its
+ *      tiles from the match counts a call before it left with the table, and so ran without the look-back,
+ *      "setop_offs_stale" = such calls whose tiles counted otherwise (contents rewritten in place under an unchanged
+ *      partition): the pass ran again with the look-back (after two in a row the context stops trying).  See ukm_setop2. */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);
@@ -378,7 +382,9 @@ int ukm_merge_k(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *const
  *      against the buffers as they are now instead of computing it again; a table that no longer fits (the buffers were
  *      rewritten in place) is computed anew.  Results never depend on this cache, only time does.  Host arrays, the n-way
  *      entries and inputs of fewer than ~2.5e6 records in total never use it; statistics "setop_part_hits" /
- *      "setop_part_stale" (ukm_ctx_get_stat). */
+ *      "setop_part_stale" (ukm_ctx_get_stat).  On plain codes the table carries the pair's match counts too, from which
+ *      the later calls know where every tile's output starts (every tile checks its own count; a difference repeats the
+ *      pass the usual way): "setop_offs_hits" / "setop_offs_stale". */
 int ukm_setop2(ukm_ctx *ctx, int op, const uint64_t *a_keys, const uint32_t *a_taxids,
                uint64_t na, const uint64_t *b_keys, const uint32_t *b_taxids, uint64_t nb,
                uint32_t flags, uint64_t *out_keys, uint32_t *out_taxids, uint64_t out_cap,

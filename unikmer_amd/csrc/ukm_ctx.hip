@@ -40,7 +40,7 @@ static const char *const UKM_OPTION_KEYS[] = {
     "sort_local", "sort_counting", "sort_fan", "win_strip", "nthash_strip", "force_ticket", "setop_src", "setop_defer", "punion_clade", "srmerge_clade", "map_sorted", "grep_lds",
     // tuning / diagnostics (developer)
     "punion_k0", "punion_claim", "punion_debug", "kway_k", "kway_r", "kway_top2", "kway_debug", "srmerge_fill", "srmerge_spr", "srmerge_buckets",
-    "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_part_reuse", "setop_fix", "map_dir_slack",
+    "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_part_reuse", "setop_offs_reuse", "setop_offs_ops", "setop_fix", "map_dir_slack",
     // test aid: the byte every arena block is filled with before a top-level call (see ws_poison_fill)
     "ws_poison",
 };
@@ -110,6 +110,8 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "sort_fused_hist") == 0) *value = c->stat_sort_fused_hist;
     else if (strcmp(key, "setop_part_hits") == 0) *value = c->stat_setop_part_hits;
     else if (strcmp(key, "setop_part_stale") == 0) *value = c->stat_setop_part_stale;
+    else if (strcmp(key, "setop_offs_hits") == 0) *value = c->stat_setop_offs_hits;
+    else if (strcmp(key, "setop_offs_stale") == 0) *value = c->stat_setop_offs_stale;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "workspace_bytes") == 0) {
         u64 t = 0;

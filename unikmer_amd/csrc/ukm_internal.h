@@ -166,12 +166,18 @@ struct ukm_ctx {
     u64 stat_count_window_retries = 0;  // ukm_count calls that repeated the window pass: its estimated buffer was too small
     u64 stat_setop_part_hits = 0;   // 2-way set operations that took their merge-path table from the partition cache (verified, see below)
     u64 stat_setop_part_stale = 0;  // ... whose cached table failed the verification: the partition ran after all
+    u64 stat_setop_offs_hits = 0;   // ... of the hits: plain-key passes that took their tiles' output offsets from the cached match counts
+    u64 stat_setop_offs_stale = 0;  // ... whose tiles counted otherwise (contents changed in place, partition intact): the pass ran again with the look-back
 
     // Partition cache of the public 2-way set operation (ukm_setops.hip: run_setop_pass).  The merge-path table depends on
     // (A, B, |A|, |B|, tile size) only -- union, inter and diff of one pair share it -- so the context keeps the table of the
     // most recent call in ONE slot of device memory of its own (never the arena: that is poisoned by tests and reused by
     // every call) and the next call on the same key VERIFIES it against the inputs as they are now instead of searching
     // again.  buf[0] = the verification's stale word (zero whenever `valid`), buf[PC_HEAD ...] = the table.
+    // Behind the table's ntiles + 1 words a second column of ntiles + 1: MP[t] = how many matched pairs of (A, B) have their A
+    // record in front of boundary t.  Every plain-key operation's tile offsets follow from it (ukm_setops.hip:
+    // setop_partition_verify_kernel), so a pass that finds it valid runs without the look-back.  Same key, same slot: it is
+    // dropped wherever the table is; `counts_valid` is set only behind a pass that came back without any flag.
     struct PartCache {
         static constexpr size_t PC_HEAD = 8;  // u64 words in front of the table: a 64-byte line
         u64 *buf = nullptr;
@@ -181,6 +187,9 @@ struct ukm_ctx {
         bool valid = false;
         int stale_run = 0;  // stale hits in a row
         bool off = false;   // two in a row (a caller that refills fixed buffers with same-sized batches): no more attempts
+        bool counts_valid = false;
+        int offs_stale_run = 0;  // passes in a row whose tiles contradicted the counts
+        bool offs_off = false;   // two in a row: no more attempts (the partition cache itself goes on)
     } part_cache;
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device

@@ -26,7 +26,9 @@ namespace {
 
 // FLAG_STALE: the launch ran on a merge-path table taken from the context's partition cache and the verification found a
 // boundary that does not hold for the inputs as they are now (setop_partition_verify_kernel): no tile has run
-enum { FLAG_DUP = 1, FLAG_UNSORTED = 2, FLAG_TIMEOUT = 4, FLAG_STALE = 8 };
+// FLAG_OFFS: the launch took its tiles' output offsets from the cached match counts (TABLE instantiation, below) and a tile
+// counted another number of records than its step of the table: the output is void, the pass runs again with the look-back
+enum { FLAG_DUP = 1, FLAG_UNSORTED = 2, FLAG_TIMEOUT = 4, FLAG_STALE = 8, FLAG_OFFS = 16 };
 
 #ifndef SETOP_NT
 #define SETOP_NT 512
@@ -71,6 +73,9 @@ struct SetopArgs {
     // the stale word of the context's partition cache when `mp` is the cached table (ukm_ctx::PartCache), else nullptr.  Non-zero:
     // the table failed its verification -- NO kernel of the launch may take an address from it.
     const u64 *stale;
+    // TABLE instantiation only: the exclusive output offset of every tile and, in [ntiles], the total -- written by
+    // setop_partition_verify_kernel from the cached match counts for THIS operation (run_setop_pass)
+    u64 *base;
 };
 constexpr u32 FIX_SLOTS = 16;
 
@@ -346,10 +351,21 @@ __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p,
 // also clears tile t's status line, block 0 the control words (what the fused kernel does on a miss).  A bad boundary sets
 // the cache's stale word -- a word of its own: an OR into the control words would race with their clearing -- and every
 // kernel of the launch behind this one returns at its top (setop_table_stale).
-__global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p, int tile_items, u32 nclear) {
+//
+// `counts` != nullptr: the launch behind this one takes its output offsets from the slot's second column instead of a
+// look-back.  counts[t] = MP[t] = how many matched pairs have their A record in front of boundary t (the merge loop
+// attributes a match to its A step, peeking at B's halo) -- a property of the pair, not of the operation.  With d_t and
+// a_t as above and s_t = [A[a_t - 1] == B[b_t]] (a matched pair that straddles the boundary; both keys are loaded for the
+// check anyway) the exclusive offset of tile t is
+//     inter: MP[t]      diff: a_t - MP[t]      union: d_t - MP[t] + s_t   (the union drops a pair's B record, in B's tile)
+// and p.base[0 .. ntiles] gets this operation's.  The column may hold anything too: MP[0] = 0 and every step within
+// 0 <= MP[t] - MP[t-1] <= a_t - a_{t-1}, or the table is stale -- which leaves 0 <= base[t] <= d_t + 1 for every operation.
+// The tile kernel then checks every tile's count against its step (FLAG_OFFS), so a table that merely belongs to other
+// contents costs a second pass, never a wrong result.  No status line is read by that launch: none is cleared.
+__global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p, int tile_items, u32 nclear, const u64 *counts, int op) {
     const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < nclear) p.result[threadIdx.x] = 0;
-    if (t < p.ntiles) p.status[t * LB_STRIDE] = 0;
+    if (!counts && t < p.ntiles) p.status[t * LB_STRIDE] = 0;
     if (t > p.ntiles) return;
     const u64 N = p.na + p.nb;
     u64 d = t * (u64)tile_items;
@@ -357,11 +373,18 @@ __global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p
     const u64 a = p.mp[t];
     const u64 lo = d > p.nb ? d - p.nb : 0, hi = d < p.na ? d : p.na;
     bool good = a >= lo && a <= hi;
+    u64 ap = 0;
     if (good && t > 0) {
         // the tile in front of this boundary: 0 <= its A items <= its items (<= tile_items), which leaves its B items >= 0 too
         const u64 dp = (t - 1) * (u64)tile_items;  // (< N: t <= ntiles)
-        const u64 ap = p.mp[t - 1];
+        ap = p.mp[t - 1];
         good = a >= ap && a - ap <= d - dp;
+    }
+    u64 m = 0, s = 0;
+    if (good && counts) {
+        m = counts[t];
+        const u64 mprev = t > 0 ? counts[t - 1] : 0;
+        good = t > 0 ? (m >= mprev && m - mprev <= a - ap) : m == 0;
     }
     if (good) {
         const u64 b = d - a;  // <= nb by a >= lo
@@ -370,8 +393,36 @@ __global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p
         const u64 a1 = p.a[t1 ? a - 1 : 0], b1 = p.b[t1 ? b : 0];
         const u64 b2 = p.b[t2 ? b - 1 : 0], a2 = p.a[t2 ? a : 0];
         good = (!t1 || a1 <= b1) && (!t2 || b2 < a2);
+        s = (t1 && a1 == b1) ? 1 : 0;
     }
     if (!good) *const_cast<u64 *>(p.stale) = 1;  // (every writer writes the same value)
+    else if (counts) p.base[t] = op == UKM_OP_INTER ? m : (op == UKM_OP_DIFF ? a - m : d - m + s);
+}
+
+// Behind a plain-key pass that ran WITH the look-back on the slot's table: every status word now holds LB_INCL | the
+// inclusive prefix of its tile, i.e. the exclusive offset of the next one.  One thread per boundary turns that -- with the
+// formulas above read the other way -- into MP[t], the slot's second column.  The host declares the column valid only after
+// the read-back of this launch shows no flag; until then nothing reads it.  (A stale table: no tile has run, nothing to do.)
+__global__ __launch_bounds__(256) void setop_counts_record_kernel(SetopArgs p, int tile_items, int op, u64 *counts) {
+    const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (t > p.ntiles || setop_table_stale(p)) return;
+    u64 m = 0;
+    if (t > 0) {
+        const u64 N = p.na + p.nb;
+        u64 d = t * (u64)tile_items;
+        if (d > N) d = N;
+        const u64 a = p.mp[t];
+        const u64 e = lb_load(&p.status[(t - 1) * LB_STRIDE]) & LB_VAL;
+        if (op == UKM_OP_INTER) m = e;
+        else if (op == UKM_OP_DIFF) m = a - e;
+        else {
+            const u64 b = d - a;
+            const bool t1 = a != 0 && a <= p.na && b < p.nb;  // (a fresh or verified table: always in range)
+            const u64 a1 = p.a[t1 ? a - 1 : 0], b1 = p.b[t1 ? b : 0];
+            m = d + ((t1 && a1 == b1) ? 1 : 0) - e;
+        }
+    }
+    counts[t] = m;
 }
 
 // UKM_OP_MERGE_INTERNAL (ukm_internal.h): plain 2-way MERGE of two non-decreasing streams, every record
@@ -1128,6 +1179,10 @@ __global__ void setop_ct_kernel(SetopArgs p, int op) {
 //   a predecessor fails to publish within LB_SPIN_LIMIT polls the kernel raises FLAG_TIMEOUT
 //   and the host re-runs with TICKET = true, where tile ids come from an atomic counter and
 //   forward progress holds for any dispatch order.
+// TABLE = true (plain keys, union / inter / diff): the tiles' output offsets are known before the launch (p.base, see
+//   setop_partition_verify_kernel).  Tile id = blockIdx.x, no ticket, nothing published, nobody waited for: the tiles are
+//   independent of each other.  A tile whose count differs from its step of the table raises FLAG_OFFS and stores no more
+//   than the step.
 // Up to 80 KB of LDS per workgroup (plain keys; taxids OR ranks riding along): two 512-thread workgroups per CU = 4
 // waves per SIMD, so the register budget is 128 and the allocator is told so (by itself it budgets 256 for a
 // 512-thread workgroup: the plain kernel came out at 129 with its two load paths, the union with taxids at 131 once
@@ -1139,10 +1194,11 @@ __global__ void setop_ct_kernel(SetopArgs p, int op) {
 #ifndef SETOP_WAVES_TAX
 #define SETOP_WAVES_TAX 6  /* per-record taxids, no ranks: THREE workgroups per CU (SETOP_VT_TAX <= 7) */
 #endif
-template <int OP, bool TAX, bool RANK, bool TICKET, int NTH, int VT, bool CT = false, bool DEFER = false>
+template <int OP, bool TAX, bool RANK, bool TICKET, int NTH, int VT, bool CT = false, bool DEFER = false, bool TABLE = false>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu((TAX && RANK) ? 2 : ((TAX && VT <= 8) ? SETOP_WAVES_TAX : SETOP_WAVES), (TAX && RANK) ? 8 : ((TAX && VT <= 8) ? SETOP_WAVES_TAX : SETOP_WAVES))))
 void setop_tile_kernel(SetopArgs p) {
     static_assert(!(CT && TAX), "CT: no per-record taxids");
+    static_assert(!TABLE || (!TAX && !RANK && !TICKET && !CT && !DEFER && OP != UKM_OP_MERGE_INTERNAL), "TABLE: plain keys only");
     constexpr int TILE = NTH * VT;
     constexpr int SLOTS = TILE + 8;
     constexpr int NP = TilePairs<NTH, VT>::NP;
@@ -1161,7 +1217,9 @@ void setop_tile_kernel(SetopArgs p) {
     u64 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     u64 tlast = clock64();
 #endif
-    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
+    u64 tile;
+    if constexpr (TABLE) tile = blockIdx.x;
+    else tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     PH(0);
     setop_resolve_sizes(p, (u64)TILE);
     // chained call: the launch covers the upper bound of |A|.  A cached partition that failed its verification: EVERY
@@ -1170,6 +1228,11 @@ void setop_tile_kernel(SetopArgs p) {
     // setop_stale_report_kernel tells the host.)
     if (tile >= p.ntiles || setop_table_stale(p)) return;
     const TileGeom g = tile_geom<NTH, VT>(p, tile);
+    u64 tbase = 0, tstep = 0;  // TABLE only: this tile's offset and its step of the table (scalar loads beside the mp words)
+    if constexpr (TABLE) {
+        tbase = sload_u64(p.base + tile);
+        tstep = sload_u64(p.base + tile + 1) - tbase;
+    }
     u32 bad = 0;
     bool fast = false;  // workgroup-uniform
 #ifndef SETOP_NO_FAST
@@ -1243,7 +1306,7 @@ void setop_tile_kernel(SetopArgs p) {
             tile_total = tot & 0xFFFFu;
             excl &= 0xFFFFu;
         }
-        if (OP != UKM_OP_MERGE_INTERNAL && tid == 0) lb_publish(p.status, tile, (u64)tile_total);
+        if (!TABLE && OP != UKM_OP_MERGE_INTERNAL && tid == 0) lb_publish(p.status, tile, (u64)tile_total);
         if (fast) bad |= tile_check_order_lds<NTH, VT>(g, tid, s_keys);
         __syncthreads();  // every thread has finished reading the tile from LDS; s_scan may be reused
     }
@@ -1260,6 +1323,8 @@ void setop_tile_kernel(SetopArgs p) {
     PH(3);
     if (OP == UKM_OP_MERGE_INTERNAL) {
         if (tid == 0) s_misc[1] = tile * (u64)TILE;  // every record is kept: the tile's output offset is known
+    } else if (TABLE) {
+        if ((u64)tile_total != tstep) bad |= FLAG_OFFS;  // (workgroup-uniform)
     } else if (tid < 64) {
         bool timed_out = false;
 #ifdef LB_PRE_SLEEP
@@ -1280,12 +1345,19 @@ void setop_tile_kernel(SetopArgs p) {
         // to the same word)
         u32 wbad = 0;
 #pragma unroll
-        for (u32 f = 1; f <= FLAG_TIMEOUT; f <<= 1)
+        for (u32 f = 1; f <= (TABLE ? FLAG_OFFS : FLAG_TIMEOUT); f <<= 1)
             if (__ballot((bad & f) != 0)) wbad |= f;
         if (wbad && lane_id() == 0) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)wbad);
     }
     __syncthreads();
-    const u64 base = s_misc[1];
+    u64 base;
+    if constexpr (TABLE) {
+        base = tbase;
+        // (a step that does not fit the tile's count, a "negative" one included: what is stored stays inside both)
+        if (tstep < (u64)tile_total) tile_total = (u32)tstep;
+    } else {
+        base = s_misc[1];
+    }
     if constexpr (DEFER) {
         if (p.fix) {  // (uniform) the pairs left to setop_taxid_fix_kernel, at their output positions
             const u32 nf = s_fix.t.n < FIX_SLOTS ? s_fix.t.n : FIX_SLOTS;
@@ -1305,7 +1377,7 @@ void setop_tile_kernel(SetopArgs p) {
             tile_flush_ct<OP, NTH, VT>(p, tid, base, tile_total, excl, mask, amask, mmask, ct_lca, reinterpret_cast<u32 *>(s_keys));
     }
 #endif
-    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tile_total;
+    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = TABLE ? tbase + tstep : base + tile_total;  // (TABLE: base[ntiles])
     PH(5);
 #ifdef UKM_PROFILE_PHASES
     if (tid == 0 && p.dbg) {
@@ -1365,6 +1437,15 @@ void launch_tile(const SetopArgs &p, hipStream_t st, bool ticket) {
     }
 }
 
+// the TABLE instantiations: plain keys, the three public operations
+template <int NTH, int VT>
+void launch_table(int op, const SetopArgs &p, hipStream_t st) {
+    const dim3 grid((unsigned)p.ntiles), block(NTH);
+    if (op == UKM_OP_UNION) hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_UNION, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);
+    else if (op == UKM_OP_INTER) hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_INTER, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_DIFF, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);
+}
+
 template <bool TAX, bool RANK, int NTH, int VT, bool CT = false, bool DEFER = false>
 void launch_op(int op, const SetopArgs &p, hipStream_t st, bool ticket) {
     if (op == UKM_OP_UNION) launch_tile<UKM_OP_UNION, TAX, RANK, NTH, VT, CT, DEFER>(p, st, ticket);
@@ -1383,6 +1464,12 @@ constexpr int VT_PLAIN = SETOP_VT;  // 19 items per thread: 76 KiB of keys in LD
 // 7 (three per CU): 3.94 / 3.66, 6: 4.08 / 3.81, 5 (four per CU, 8 waves per SIMD): 4.01 / 3.72.
 #ifndef SETOP_VT_TAX
 #define SETOP_VT_TAX 7
+#endif
+// Operations that take their tile offsets from the cached match counts, 1 << op each (union 1, inter 2, diff 4).  The union
+// keeps the look-back: it writes 10.7 GB at 2 x 1e9 and its look-back waits hide behind the stores -- its TABLE kernel was
+// no faster than the spread between runs (profiles/offs_reuse_notes.md section 3), inter's is 0.4 ms faster.
+#ifndef SETOP_OFFS_OPS
+#define SETOP_OFFS_OPS 6
 #endif
 constexpr int VT_TAX = SETOP_VT_TAX;
 constexpr int VT_RANK = 12;  // ranks ride along (the multiset re-run), with or without taxids
@@ -1450,12 +1537,14 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     bool cache = may_cache && fused && !rank && na && nb && !pc.off && !ukm_env_is(c, "UKM_SETOP_PART_REUSE", '0');
     bool hit = false;
     if (cache) {
-        const size_t need = ukm_ctx::PartCache::PC_HEAD + (size_t)p.ntiles + 1;
+        // (the table and, behind it, the match counts: PartCache)
+        const size_t need = ukm_ctx::PartCache::PC_HEAD + 2 * ((size_t)p.ntiles + 1);
         if (pc.cap_words < need) {  // grown on demand; the slot's table goes with the old buffer
             if (pc.buf) (void)hipFree(pc.buf);
             pc.buf = nullptr;
             pc.cap_words = 0;
             pc.valid = false;
+            pc.counts_valid = false;
             void *nb_ = nullptr;
             if (hipMalloc(&nb_, need * sizeof(u64)) == hipSuccess) {
                 pc.buf = (u64 *)nb_;
@@ -1472,9 +1561,23 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
         p.stale = pc.buf;
         p.mp = pc.buf + ukm_ctx::PartCache::PC_HEAD;
     }
+    // The match counts MP of the slot (its second column; setop_partition_verify_kernel has the formulas): a plain-key
+    // union / inter / diff that hits the partition cache while they are valid takes its tiles' output offsets from them --
+    // the TABLE instantiation, no look-back -- and every other such pass on the slot's table records them behind its
+    // look-back.  UKM_SETOP_OFFS_REUSE=0 turns both off; UKM_SETOP_OFFS_OPS (developer knob) = which operations use the
+    // counts, 1 << op each (profiles/offs_reuse_notes.md has the measurements behind the default).
+    const bool plain3 = !tax && !ct && !rank && (op == UKM_OP_UNION || op == UKM_OP_INTER || op == UKM_OP_DIFF);
+    const bool offs_on = cache && plain3 && !pc.offs_off && !ukm_env_is(c, "UKM_SETOP_OFFS_REUSE", '0');
+    u64 *const counts = cache ? p.mp + p.ntiles + 1 : nullptr;
+    bool counts_good = cache && hit && pc.counts_valid;  // the column still belongs to the table this pass works on
+    if (cache) pc.counts_valid = false;                   // (like `valid`: until this pass has come back)
+    bool table = offs_on && counts_good && ((ukm_env_int(c, "UKM_SETOP_OFFS_OPS", SETOP_OFFS_OPS) >> op) & 1) != 0;
+    bool recorded = false;
     if (hit) {
         const unsigned vblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
-        hipLaunchKernelGGL(setop_partition_verify_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
+        p.base = blk.tail;  // (the arena's table words, which p.mp does not occupy on a cached pass)
+        hipLaunchKernelGGL(setop_partition_verify_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD,
+                           table ? (const u64 *)counts : (const u64 *)nullptr, op);
         UKM_HIP(hipGetLastError());
     } else if (fused) {
         const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
@@ -1499,7 +1602,9 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     // (the bracket holds the tile kernel with its CT / fix / gather kernels, not the partition)
     const LbLaunch how = {"setop", "set-op kernel", FLAG_TIMEOUT, true, false, fused};
     const auto launch_tiles = [&](bool ticket) {
-        if (rank) {
+        if (table) {
+            launch_table<NTS, VT_PLAIN>(op, p, c->stream);
+        } else if (rank) {
             if (tax) launch_op<true, true, NTS, VT_RANK>(op, p, c->stream, ticket);
             else if (ct) launch_op<false, true, NTS, VT_RANK, true>(op, p, c->stream, ticket);
             else launch_op<false, true, NTS, VT_RANK>(op, p, c->stream, ticket);
@@ -1511,6 +1616,10 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
             else if (ct) launch_op<false, false, NTS, VT_PLAIN, true>(op, p, c->stream, ticket);
             else launch_op<false, false, NTS, VT_PLAIN>(op, p, c->stream, ticket);
         }
+        if (offs_on && !table && !counts_good) {
+            hipLaunchKernelGGL(setop_counts_record_kernel, dim3((unsigned)((p.ntiles + 1 + 255) / 256)), dim3(256), 0, c->stream, p, (int)tile_items, op, counts);
+            recorded = true;
+        }
         if (p.stale) hipLaunchKernelGGL(setop_stale_report_kernel, dim3(1), dim3(1), 0, c->stream, p);
         return UKM_OK;
     };
@@ -1521,6 +1630,8 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
             // search after all -- its kernel clears the stale word and the control block -- and the launch again, once.
             c->stat_setop_part_stale++;
             if (++pc.stale_run >= 2) pc.off = true;
+            table = false;  // the counts go with the table: this pass records fresh ones
+            counts_good = false;
             const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
             hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
             UKM_HIP(hipGetLastError());
@@ -1528,12 +1639,35 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
         } else {
             c->stat_setop_part_hits++;
             pc.stale_run = 0;
+            if (table) {
+                const u64 fl = result_host[1];
+                if ((fl & FLAG_OFFS) && !(fl & (FLAG_DUP | FLAG_UNSORTED))) {
+                    // The contents changed in place under an intact partition: some tile counted another number of records
+                    // than its step.  The output is void; the pass again, once, with the look-back (cleared control block and
+                    // status lines: the verification cleared no status line) -- which records fresh counts.
+                    c->stat_setop_offs_stale++;
+                    if (++pc.offs_stale_run >= 2) pc.offs_off = true;
+                    table = false;
+                    counts_good = false;
+                    LbLaunch again = how;
+                    again.first_zeroed = false;
+                    UKM_TRY(ukm_lb_launch(c, blk, again, launch_tiles, result_host));
+                } else if (!(fl & FLAG_OFFS)) {
+                    c->stat_setop_offs_hits++;
+                    pc.offs_stale_run = 0;
+                }
+                // (duplicates or disorder beside FLAG_OFFS: the caller discards this pass anyway -- no second one)
+                if (result_host[1] & FLAG_OFFS) counts_good = false;
+                result_host[1] &= ~(u64)FLAG_OFFS;
+            }
         }
     }
     if (result_host[1] & FLAG_STALE) UKM_FAIL(UKM_ERR_HIP, "setop: a fresh partition table failed its verification");
     if (cache) {  // the table in the slot belongs to this pass's inputs as they were a moment ago
         pc.a = a; pc.b = b; pc.na = na; pc.nb = nb; pc.tile_items = tile_items;
         pc.valid = true;
+        // the counts: kept or freshly recorded, and only behind a pass that came back with no flag at all
+        pc.counts_valid = (counts_good || recorded) && result_host[1] == 0;
     }
 #ifdef UKM_PROFILE_PHASES
     {
