@@ -16,6 +16,11 @@
  *    staged through the context's device workspace.  Scalar outputs (n_out) are host
  *    pointers.  All buffers are caller-owned; nothing is retained after the call returns
  *    (cgo pointer-passing rules), except the taxonomy which is copied into the context.
+ *  - Alignment: a device pointer needs only the natural alignment of its element type -- 8 bytes for codes, offsets and
+ *    uint64 outputs, 4 for taxids, 1 for bases and uint8 outputs -- so streams may be sub-allocated back to back from one
+ *    slab.  Results never depend on the address.  A call reads nothing as data, and writes nothing, outside the arrays it
+ *    was given: whatever lies in front of or behind an array (a neighbour's records included) has no influence on the
+ *    result and is left as it was.
  *  - Outputs are caller-allocated with capacity `out_cap` (elements); upper bounds:
  *    union <= sum(n), inter <= n[0], diff <= n[0], common <= sum(n), unique <= n (2n for
  *    UKM_REPEATED_CHUNK), encode/nthash <= number of windows.  Too small -> UKM_ERR_CAPACITY.

@@ -24,8 +24,8 @@ from conftest import splitmix64, synth_tree
 
 SEED = 0x756E696B6D6572
 FRONT = 64                      # elements of the front guard (256 / 512 bytes: the slice stays 16-byte aligned)
-SENT = {np.dtype(np.uint64): 0xA5A5A5A55A5A5A5A, np.dtype(np.uint32): 0xA5A55A5A}
-SIGNED = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}
+SENT = {np.dtype(np.uint64): 0xA5A5A5A55A5A5A5A, np.dtype(np.uint32): 0xA5A55A5A, np.dtype(np.uint8): 0xA5}
+SIGNED = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32, np.dtype(np.uint8): np.uint8}
 U64, U32 = np.uint64, np.uint32
 
 # records per tile, from the kernels' sources
@@ -192,8 +192,9 @@ class Case:
     def bound(self):
         return int(self._bound(*self.data()))
 
-    def call(self, ctx, L, outs):
-        return self._call(ctx, L, outs, *self.data())
+    def call(self, ctx, L, outs, data=None):
+        """data: the case's inputs held elsewhere (test_gpu_alignment.py: device views of them), in the order of data()"""
+        return self._call(ctx, L, outs, *(self.data() if data is None else data))
 
 
 CASES = {}
@@ -574,12 +575,13 @@ def test_case_table_oracle_only():
 
 # ---- the helper every GPU case goes through ---------------------------------------------------------------------------------
 class Guarded:
-    """one output array: [front guard | cap | back guard], all sentinel; the call gets the middle"""
+    """one output array: [front guard | cap | back guard], all sentinel; the call gets the middle.  shift: the front guard
+    is FRONT + shift elements, so the middle starts `shift` elements behind a 16-byte boundary"""
 
-    def __init__(self, dtype, cap, bound, place):
-        self.dt, self.cap = np.dtype(dtype), cap
+    def __init__(self, dtype, cap, bound, place, shift=0):
+        self.dt, self.cap, self.front = np.dtype(dtype), cap, FRONT + shift
         back = max(bound - cap, 0) + 64
-        host = np.full(FRONT + cap + back, SENT[self.dt], dtype=self.dt)
+        host = np.full(self.front + cap + back, SENT[self.dt], dtype=self.dt)
         if place == "device":
             import torch
             self.buf = torch.from_numpy(host.view(SIGNED[self.dt])).cuda()
@@ -588,7 +590,7 @@ class Guarded:
             self.buf = host
             ptr = host.ctypes.data
         assert ptr % 16 == 0
-        self.mid = self.buf[FRONT:FRONT + cap]
+        self.mid = self.buf[self.front:self.front + cap]
 
     def host(self):
         return self.buf.cpu().numpy().view(self.dt) if hasattr(self.buf, "cpu") else self.buf
@@ -596,21 +598,22 @@ class Guarded:
     def check(self, what):
         h = self.host()
         bad = np.flatnonzero(h != self.dt.type(SENT[self.dt]))
-        bad = bad[(bad < FRONT) | (bad >= FRONT + self.cap)] - FRONT
+        bad = bad[(bad < self.front) | (bad >= self.front + self.cap)] - self.front
         assert len(bad) == 0, "%s: %d guard words written, at offsets %s from the start of the buffer of %d" % (what, len(bad), bad[:8].tolist(), self.cap)
 
     def head(self, n):
-        return self.host()[FRONT:FRONT + n]
+        return self.host()[self.front:self.front + n]
 
 
-def attempt(ctx, L, case, cap, place):
+def attempt(ctx, L, case, cap, place, shifts=None, data=None):
+    """shifts: one Guarded shift per output array; data: see Case.call"""
     exp = case.expected()
     need = len(exp[0])
     what = "%s, out_cap = %d (need %d, bound %d), %s outputs" % (case.name, cap, need, case.bound, place)
-    bufs = [Guarded(dt, cap, case.bound, place) for dt in case.dtypes]
+    bufs = [Guarded(dt, cap, case.bound, place, shift=s) for dt, s in zip(case.dtypes, shifts or [0] * len(case.dtypes))]
     err = res = None
     try:
-        res = case.call(ctx, L, [b.mid for b in bufs])
+        res = case.call(ctx, L, [b.mid for b in bufs], data)
     except L.CapacityError as e:
         err = e
     for i, b in enumerate(bufs):

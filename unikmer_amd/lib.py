@@ -385,12 +385,14 @@ class Context:
         _check(self.L.ukm_taxonomy_max_taxid(self.h, C.byref(v)))
         return v.value
 
-    def lca(self, a, b):
+    def lca(self, a, b, out=None):
         pa, n, k1 = _ptr(a, np.uint32)
         pb, n2, k2 = _ptr(b, np.uint32)
         assert n == n2
-        out = _empty_like_kind(a, n, np.uint32)
-        po, _, _ = _ptr(out, np.uint32)
+        if out is None:
+            out = _empty_like_kind(a, n, np.uint32)
+        po, no, _ = _ptr(out, np.uint32)
+        assert no >= n
         _check(self.L.ukm_lca(self.h, pa, pb, n, po))
         return out[:n]
 
@@ -409,11 +411,13 @@ class Context:
         _check(load().ukm_rank_filter_plan(C.addressof(f), sa.ctypes.data, wa.ctypes.data))
         return sa, wa
 
-    def rank_pass(self, f, taxids):
+    def rank_pass(self, f, taxids, out=None):
         """1 where a record with that taxid passes the RankFilter, else 0 (rfilter.go:438-520)"""
         pt, n, k1 = _ptr(taxids, np.uint32)
-        out = _empty_like_kind(taxids, n, np.uint8)
-        po, _, _ = _ptr(out, np.uint8)
+        if out is None:
+            out = _empty_like_kind(taxids, n, np.uint8)
+        po, no, _ = _ptr(out, np.uint8)
+        assert no >= n
         _check(self.L.ukm_rank_pass(self.h, C.addressof(f), pt, n, po))
         return out[:n]
 
@@ -716,6 +720,9 @@ class Context:
                 tp[i] = pt
                 keep.append(kt)
         total = sum(int(lens[i]) for i in range(n))
+        # (as on the path above: _nway looks at the last entry to see whether EVERY stream pointer is a device pointer)
+        on_device = n > 0 and all(_is_torch(a) and a.is_cuda for a in keep if a is not None)
+        keep.append("device" if on_device else "host")
         return kp, (tp if tax else None), lens, n, tax or bool(ft and ft[1]), total, keep, ft
 
     def _nway(self, which, keys_list, taxids_list, bound, extra, flags, out, out_taxids):
@@ -881,9 +888,13 @@ class Context:
         _check(self.L.ukm_shard_exchange_known(self.h, pk, pt, sc.ctypes.data, rc.ctypes.data, po, pot, cap, C.byref(m)))
         return out[: m.value], (out_t[: m.value] if out_t is not None else None), rc
 
-    def partition_points(self, keys, splitters):
+    def partition_points(self, keys, splitters, out=None):
+        """splitters (and out, the cuts) may be device tensors: the C ABI takes them where they are"""
         pk, n, k1 = _ptr(keys, np.uint64)
-        sp = np.ascontiguousarray(splitters, dtype=np.uint64)
-        cuts = np.empty(len(sp), dtype=np.uint64)
-        _check(self.L.ukm_partition_points(self.h, pk, n, sp.ctypes.data, len(sp), cuts.ctypes.data))
-        return cuts
+        sp = splitters if _is_torch(splitters) else np.ascontiguousarray(splitters, dtype=np.uint64)
+        ps, ns, k2 = _ptr(sp, np.uint64)
+        cuts = out if out is not None else _empty_like_kind(sp, ns, np.uint64)
+        pc, nc, k3 = _ptr(cuts, np.uint64)
+        assert nc >= ns
+        _check(self.L.ukm_partition_points(self.h, pk, n, ps, ns, pc))
+        return cuts[:ns]
