@@ -180,16 +180,59 @@ struct ukm_ctx {
     // dropped wherever the table is; `counts_valid` is set only behind a pass that came back without any flag.
     struct PartCache {
         static constexpr size_t PC_HEAD = 8;  // u64 words in front of the table: a 64-byte line
+        struct Key {
+            const u64 *a = nullptr, *b = nullptr;
+            u64 na = 0, nb = 0, tile_items = 0;
+            bool operator==(const Key &o) const { return a == o.a && b == o.b && na == o.na && nb == o.nb && tile_items == o.tile_items; }
+        };
         u64 *buf = nullptr;
         size_t cap_words = 0;
-        const u64 *a = nullptr, *b = nullptr;
-        u64 na = 0, nb = 0, tile_items = 0;
+        Key key;
         bool valid = false;
         int stale_run = 0;  // stale hits in a row
         bool off = false;   // two in a row (a caller that refills fixed buffers with same-sized batches): no more attempts
         bool counts_valid = false;
         int offs_stale_run = 0;  // passes in a row whose tiles contradicted the counts
         bool offs_off = false;   // two in a row: no more attempts (the partition cache itself goes on)
+
+        u64 *stale_word() const { return buf; }
+        u64 *table() const { return buf + PC_HEAD; }
+        u64 *counts(u64 ntiles) const { return table() + ntiles + 1; }
+        // Room for a table and a count column of ntiles + 1 words each.  Grown on demand: the slot's contents go with the old
+        // buffer.  false = no memory for a cache: the call goes on without one.
+        bool reserve(u64 ntiles) {
+            const size_t need = PC_HEAD + 2 * ((size_t)ntiles + 1);
+            if (cap_words >= need) return true;
+            if (buf) (void)hipFree(buf);
+            buf = nullptr;
+            cap_words = 0;
+            valid = counts_valid = false;
+            void *nbuf = nullptr;
+            if (hipMalloc(&nbuf, need * sizeof(u64)) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+            buf = (u64 *)nbuf;
+            cap_words = need;
+            return true;
+        }
+        // A pass on key k begins: is the slot's table k's, and are its counts usable?  The slot holds NOTHING until commit(): an
+        // error on the way leaves no key behind.
+        struct Opened { bool hit, counts; };
+        Opened open(const Key &k) {
+            const Opened o = {valid && key == k, valid && key == k && counts_valid};
+            valid = counts_valid = false;
+            return o;
+        }
+        // the pass has come back: the table in the slot belongs to k's inputs as they were a moment ago
+        void commit(const Key &k, bool counts) {
+            key = k;
+            valid = true;
+            counts_valid = counts;
+        }
+        // the verdicts of the passes that tried: two bad ones in a row end the attempts for the context's lifetime
+        void note_table(bool stale) { if (!stale) stale_run = 0; else if (++stale_run >= 2) off = true; }
+        void note_counts(bool stale) { if (!stale) offs_stale_run = 0; else if (++offs_stale_run >= 2) offs_off = true; }
     } part_cache;
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device

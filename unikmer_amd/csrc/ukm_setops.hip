@@ -3,8 +3,9 @@
 // hash-map / 2-pointer loops (union.go:186-208, inter.go:205-278, diff.go:379-454).
 //
 // Design (HBM-bound integer path, no MFMA):
-//   1. partition kernel  — one thread per tile boundary binary-searches the merge path
-//                          (A before B on ties) -> mp[t]; ~30 dependent loads, massively parallel.
+//   1. partition kernel  — the merge-path split of every tile boundary (A before B on ties) -> mp[t], in two
+//                          levels: every 64th boundary by a wave's 64-ary search over the whole inputs, the
+//                          others by a thread's bracketed binary search between two of those; one launch.
 //   2. tile kernel       — one 256-thread workgroup per tile of TILE = NT*VT merged items:
 //        * coalesced loads of the tile's A range and B range (+1-element halos) into LDS,
 //        * per-thread merge-path search in LDS, then a VT-step serial merge that decides
@@ -107,12 +108,13 @@ __device__ __forceinline__ bool key_eq(u64 ka, u32 ra, u64 kb, u32 rb) {
     return ka == kb;
 }
 
-// Merge-path split of every tile boundary.  With 2.4e5 tiles a 30-step search over the whole
-// inputs per boundary is ~7e6 dependent random reads across 16 GB (0.3 ms, TLB-miss bound), so
-// the search is done in two levels: LEVEL 1 places every PART_COARSE-th boundary (and the last
-// one) with a full search, LEVEL 2 searches the others only between their two coarse neighbours
-// (the path is monotone), i.e. inside a few MB that the group's threads share in cache.
-// LEVEL 0 = single-level search of every boundary (small inputs).
+// ---- the merge-path partition: mp[t] = how many records of A lie in front of tile boundary t (A before B on ties) ----
+// With 2.4e5 tiles a 30-step search over the whole inputs per boundary is ~7e6 dependent random reads across 16 GB
+// (0.3 ms, TLB-miss bound), so the search is done in two levels: the COARSE level places every PART_COARSE-th boundary
+// (and the last one) with a full search, one wave per boundary; the FINE level searches the others only between their
+// two coarse neighbours (the path is monotone), i.e. inside a few MB that the group's threads share in cache, one thread
+// per boundary.  Small inputs: every boundary by the coarse level's search (single level).  The search itself is written
+// once, in the mp_ helpers; the kernels below are index mappings around them.
 #ifndef SETOP_PART_COARSE
 #define SETOP_PART_COARSE 64
 #endif
@@ -123,119 +125,65 @@ __device__ __forceinline__ bool key_eq(u64 ka, u32 ra, u64 kb, u32 rb) {
 #define SETOP_PART_INTERP 512  // half-width of the bracket around the interpolated split (0: plain binary search)
 #endif
 constexpr int PART_COARSE = SETOP_PART_COARSE;
-template <bool RANK, int LEVEL>
-__global__ void setop_partition_kernel(SetopArgs p, int tile_items) {
-    setop_resolve_sizes(p, (u64)tile_items);
-    u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (LEVEL == 1) {
-        t *= PART_COARSE;
-        if (t > p.ntiles + PART_COARSE - 1) return;
-        if (t > p.ntiles) t = p.ntiles;
-    } else {
-        if (LEVEL == 0 && t < p.zero_status) p.status[t * LB_STRIDE] = 0;
-        if (t > p.ntiles) return;
-        if (LEVEL == 2 && (t % PART_COARSE == 0 || t == p.ntiles)) return;  // placed by level 1
-    }
+
+// diagonal of boundary t and the legal range [lo, hi] of its split
+struct MpDiag { u64 diag, lo, hi; };
+__device__ __forceinline__ MpDiag mp_diag(const SetopArgs &p, u64 t, int tile_items) {
     const u64 N = p.na + p.nb;
     u64 diag = t * (u64)tile_items;
     if (diag > N) diag = N;
-    u64 lo = diag > p.nb ? diag - p.nb : 0;
-    u64 hi = diag < p.na ? diag : p.na;
-    if (LEVEL == 2) {
-        const u64 c0 = t / PART_COARSE * PART_COARSE;
-        const u64 c1 = (c0 + PART_COARSE < p.ntiles) ? c0 + PART_COARSE : p.ntiles;
-        const u64 l0 = p.mp[c0], h0 = p.mp[c1];
-        lo = lo > l0 ? lo : l0;
-        hi = hi < h0 ? hi : h0;
-#if SETOP_PART_INTERP
-        // The path between two coarse neighbours is close to a straight line when the keys are spread evenly (k-mer
-        // codes, hashes): two probes SETOP_PART_INTERP positions either side of the interpolated split usually bracket
-        // it, and the search that follows stays inside a few KB (the probes of a plain binary search over the window
-        // each touch another page).  Whatever the probes say narrows [lo, hi] correctly, so skewed inputs only lose
-        // the two probes.
-        if (lo < hi) {
-            const u64 W = SETOP_PART_INTERP;
-            u64 est = l0 + (h0 - l0) * (t - c0) / (c1 - c0);
-            est = est < lo ? lo : (est > hi ? hi : est);
-            const u64 L = est > lo + W ? est - W : lo;
-            const u64 R = est + W < hi ? est + W : hi;
-            bool pl = true, pr = false;
-            if (L > lo) { const u64 j = diag - L; pl = key_le<RANK>(p.a[L - 1], RANK ? p.ra[L - 1] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-            if (R < hi) { const u64 j = diag - 1 - R; pr = key_le<RANK>(p.a[R], RANK ? p.ra[R] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-            if (L > lo) { if (pl) lo = L; else hi = L - 1; }
-            if (R < hi) { if (!pr) hi = R; else lo = R + 1; }  // (R < hi fails when the left probe already cut below R)
-        }
-#endif
-    }
-    while (lo < hi) {
-        u64 mid = (lo + hi) >> 1;
-        u64 j = diag - 1 - mid;
-        bool le = key_le<RANK>(p.a[mid], RANK ? p.ra[mid] : 0, p.b[j], RANK ? p.rb[j] : 0);
-        if (le) lo = mid + 1; else hi = mid;
-    }
-    p.mp[t] = lo;
+    return {diag, diag > p.nb ? diag - p.nb : 0, diag < p.na ? diag : p.na};
 }
 
-// Wave-cooperative variant of levels 0 and 1: ONE WAVE per boundary, 64-ary search.  Each round the 64 lanes
-// probe 64 split candidates at once (the predicate is monotone along the diagonal, so the true lanes form a
-// prefix and a ballot + popcount narrows [lo, hi) to one of 65 sub-ranges): log64 instead of log2 dependent
-// round trips -- 4-5 instead of 20-30 for the few boundaries of a small input or of the coarse level, whose
-// cost is pure latency (measured: level 1 at 2 x 1e9 40 us, the single-level kernel of a 2 x 1e6 call 12 us).
-template <bool RANK, int LEVEL>
-__global__ void setop_partition_coop_kernel(SetopArgs p, int tile_items) {
-    static_assert(LEVEL == 0 || LEVEL == 1, "bulk level 2 stays one thread per boundary");
-    setop_resolve_sizes(p, (u64)tile_items);
-    const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (LEVEL == 0 && p.zero_status) {
-        // status lines of the launch's upper bound of tiles: 64 per wave
-        const u64 line = gid;
-        if (line < p.zero_status) p.status[line * LB_STRIDE] = 0;
+// the probe: does A[i] come in front of its partner on the diagonal, B[diag - 1 - i]?  (monotone in i: true, then false)
+template <bool RANK>
+__device__ __forceinline__ bool mp_le(const SetopArgs &p, u64 diag, u64 i) {
+    const u64 j = diag - 1 - i;
+    return key_le<RANK>(p.a[i], RANK ? p.ra[i] : 0, p.b[j], RANK ? p.rb[j] : 0);
+}
+
+// The path is close to a straight line when the keys are spread evenly (k-mer codes, hashes): two probes W positions
+// either side of an interpolated split `est` usually bracket it, and the search that follows stays inside a few KB (the
+// probes of a plain binary search over the window each touch another page).  Whatever the probes say narrows [lo, hi]
+// correctly, so skewed inputs only lose the two probes.  Needs lo < hi.
+template <bool RANK>
+__device__ __forceinline__ void mp_bracket(const SetopArgs &p, u64 diag, u64 est, u64 W, u64 &lo, u64 &hi) {
+    est = est < lo ? lo : (est > hi ? hi : est);
+    const u64 L = est > lo + W ? est - W : lo;
+    const u64 R = est + W < hi ? est + W : hi;
+    bool pl = true, pr = false;
+    if (L > lo) pl = mp_le<RANK>(p, diag, L - 1);
+    if (R < hi) pr = mp_le<RANK>(p, diag, R);
+    if (L > lo) { if (pl) lo = L; else hi = L - 1; }
+    if (R < hi) { if (!pr) hi = R; else lo = R + 1; }  // (R < hi fails when the left probe already cut below R)
+}
+
+// one thread: binary search
+template <bool RANK>
+__device__ __forceinline__ u64 mp_search_thread(const SetopArgs &p, u64 diag, u64 lo, u64 hi) {
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (mp_le<RANK>(p, diag, mid)) lo = mid + 1; else hi = mid;
     }
-    u64 t = gid >> 6;
-    const int lane = (int)(threadIdx.x & 63);
-    if (LEVEL == 1) {
-        t *= PART_COARSE;
-        if (t > p.ntiles + PART_COARSE - 1) return;
-        if (t > p.ntiles) t = p.ntiles;
-    } else if (t > p.ntiles) {
-        return;
-    }
-    const u64 N = p.na + p.nb;
-    u64 diag = t * (u64)tile_items;
-    if (diag > N) diag = N;
-    u64 lo = diag > p.nb ? diag - p.nb : 0;
-    u64 hi = diag < p.na ? diag : p.na;
-#if SETOP_PART_INTERP1
-    if (lo < hi) {
-        // evenly spread keys: the split of diagonal d lies near d * |A| / (|A| + |B|); two (wave-uniform) probes either
-        // side of it cut two or three of the five 64-ary rounds.  Skewed inputs only lose the probes.
-        const u64 W = SETOP_PART_INTERP1;
-        u64 est = (u64)((double)diag * ((double)p.na / (double)N));
-        est = est < lo ? lo : (est > hi ? hi : est);
-        const u64 L = est > lo + W ? est - W : lo;
-        const u64 R = est + W < hi ? est + W : hi;
-        bool pl = true, pr = false;
-        if (L > lo) { const u64 j = diag - L; pl = key_le<RANK>(p.a[L - 1], RANK ? p.ra[L - 1] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-        if (R < hi) { const u64 j = diag - 1 - R; pr = key_le<RANK>(p.a[R], RANK ? p.ra[R] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-        if (L > lo) { if (pl) lo = L; else hi = L - 1; }
-        if (R < hi) { if (!pr) hi = R; else lo = R + 1; }
-    }
-#endif
-    while (lo < hi) {  // wave-uniform
+    return lo;
+}
+
+// One wave: 64-ary search.  Each round the 64 lanes probe 64 split candidates at once (the predicate is monotone along
+// the diagonal, so the true lanes form a prefix and a ballot + popcount narrows [lo, hi) to one of 65 sub-ranges): log64
+// instead of log2 dependent round trips -- 4-5 instead of 20-30 for the few boundaries of a small input or of the coarse
+// level, whose cost is pure latency (measured: the coarse level at 2 x 1e9 40 us, the single-level kernel of a 2 x 1e6
+// call 12 us).  [lo, hi] wave-uniform; the split comes back in every lane.
+template <bool RANK>
+__device__ __forceinline__ u64 mp_search_wave(const SetopArgs &p, u64 diag, u64 lo, u64 hi, int lane) {
+    while (lo < hi) {
         const u64 span = hi - lo;
         // candidates: strictly increasing positions in [lo, hi); fewer than 64 when the span is short
-        const u64 step_n = span <= 64 ? 1 : 0;
-        const u64 cand = step_n ? lo + (u64)lane
-                                : lo + (span / 65) * (u64)(lane + 1) + ((span % 65) * (u64)(lane + 1)) / 65;  // = lo + span*(lane+1)/65, no overflow
+        const u64 cand = span <= 64 ? lo + (u64)lane
+                                    : lo + (span / 65) * (u64)(lane + 1) + ((span % 65) * (u64)(lane + 1)) / 65;  // = lo + span*(lane+1)/65, no overflow
         const bool active = cand < hi;
-        bool le = false;
-        if (active) {
-            const u64 j = diag - 1 - cand;
-            le = key_le<RANK>(p.a[cand], RANK ? p.ra[cand] : 0, p.b[j], RANK ? p.rb[j] : 0);
-        }
+        const bool le = active && mp_le<RANK>(p, diag, cand);
         const u64 m_le = __ballot(le), m_act = __ballot(active);
-        const int n_true = __popcll(m_le);            // lanes 0 .. n_true-1 are true (monotone)
-        const int n_act = __popcll(m_act);
+        const int n_true = __popcll(m_le), n_act = __popcll(m_act);  // lanes 0 .. n_true-1 are true (monotone)
         // first false candidate = lane n_true (if active) -> new hi; last true candidate -> new lo
         const u64 c_last_true = __shfl(cand, n_true > 0 ? n_true - 1 : 0, 64);
         const u64 c_first_false = __shfl(cand, n_true < 64 ? n_true : 63, 64);
@@ -244,14 +192,71 @@ __global__ void setop_partition_coop_kernel(SetopArgs p, int tile_items) {
         lo = nlo;
         hi = nhi;
     }
-    if (lane == 0) p.mp[t] = lo;
+    return lo;
+}
+
+// boundary t over the whole inputs, by one wave (the coarse level; the single level)
+template <bool RANK>
+__device__ __forceinline__ u64 mp_split_wave(const SetopArgs &p, u64 t, int tile_items, int lane) {
+    const MpDiag d = mp_diag(p, t, tile_items);
+    u64 lo = d.lo, hi = d.hi;
+#if SETOP_PART_INTERP1
+    // evenly spread keys: the split of diagonal d lies near d * |A| / (|A| + |B|); the two (wave-uniform) probes cut two or
+    // three of the five 64-ary rounds
+    if (lo < hi) mp_bracket<RANK>(p, d.diag, (u64)((double)d.diag * ((double)p.na / (double)(p.na + p.nb))), SETOP_PART_INTERP1, lo, hi);
+#endif
+    return mp_search_wave<RANK>(p, d.diag, lo, hi, lane);
+}
+
+// boundary t between its coarse neighbours c0 < t < c1, whose splits are l0 and h0, by one thread (the fine level)
+template <bool RANK>
+__device__ __forceinline__ u64 mp_split_between(const SetopArgs &p, u64 t, int tile_items, u64 c0, u64 c1, u64 l0, u64 h0) {
+    const MpDiag d = mp_diag(p, t, tile_items);
+    u64 lo = d.lo > l0 ? d.lo : l0;
+    u64 hi = d.hi < h0 ? d.hi : h0;
+#if SETOP_PART_INTERP
+    if (lo < hi) mp_bracket<RANK>(p, d.diag, l0 + (h0 - l0) * (t - c0) / (c1 - c0), SETOP_PART_INTERP, lo, hi);
+#endif
+    return mp_search_thread<RANK>(p, d.diag, lo, hi);
+}
+
+// The fine level as a kernel of its own (behind the coarse one below), one thread per boundary: a chained link of many
+// tiles, and a pass under UKM_SETOP_FUSED_PART=0.
+template <bool RANK>
+__global__ void setop_partition_fine_kernel(SetopArgs p, int tile_items) {
+    setop_resolve_sizes(p, (u64)tile_items);
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.ntiles || t % PART_COARSE == 0) return;  // (the last boundary too: placed by the coarse level)
+    const u64 c0 = t / PART_COARSE * PART_COARSE;
+    const u64 c1 = (c0 + PART_COARSE < p.ntiles) ? c0 + PART_COARSE : p.ntiles;
+    p.mp[t] = mp_split_between<RANK>(p, t, tile_items, c0, c1, p.mp[c0], p.mp[c1]);
+}
+
+// ONE WAVE per boundary.  COARSE: every PART_COARSE-th boundary and the last one; else every boundary (single level), and
+// the launch then also clears p.zero_status status lines, 64 per wave (a chained link with few tiles: one launch less).
+template <bool RANK, bool COARSE>
+__global__ void setop_partition_wave_kernel(SetopArgs p, int tile_items) {
+    setop_resolve_sizes(p, (u64)tile_items);
+    const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!COARSE && gid < p.zero_status) p.status[gid * LB_STRIDE] = 0;
+    u64 t = gid >> 6;
+    const int lane = (int)(threadIdx.x & 63);
+    if (COARSE) {
+        t *= PART_COARSE;
+        if (t > p.ntiles + PART_COARSE - 1) return;
+        if (t > p.ntiles) t = p.ntiles;
+    } else if (t > p.ntiles) {
+        return;
+    }
+    const u64 a = mp_split_wave<RANK>(p, t, tile_items, lane);
+    if (lane == 0) p.mp[t] = a;
 }
 
 // Both levels AND the clearing of the status lines in ONE launch (round 4): a workgroup owns one coarse segment of
 // PART_COARSE boundaries.  Waves 0 and 1 place the segment's two coarse ends with the 64-ary search (every coarse end is
 // found twice, by its two neighbouring segments: ~10 of them per CU, pure latency), the other boundaries are then searched
 // between the two by one thread each, and the segment's status lines (and, by segment 0, the control words) are zeroed on
-// the way.  Replaces hipMemsetAsync + the level-1 kernel + the level-2 kernel in front of every tile kernel of a plain
+// the way.  Replaces hipMemsetAsync + the coarse kernel + the fine kernel in front of every tile kernel of a plain
 // call: three launches and two dependent kernel tails less (2 x 1e9 codes: 0.19 -> see profiles/r04_notes.md).
 template <bool RANK>
 __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p, int tile_items, u32 nclear) {
@@ -259,88 +264,40 @@ __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p,
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 c0 = (u64)blockIdx.x * PART_COARSE;
     const u64 c1 = (c0 + PART_COARSE < p.ntiles) ? c0 + PART_COARSE : p.ntiles;
-    const u64 N = p.na + p.nb;
     // status lines of this segment's tiles; the control words in front of them
     if (tid < PART_COARSE && c0 + (u64)tid < p.ntiles) p.status[(c0 + (u64)tid) * LB_STRIDE] = 0;
     if (blockIdx.x == 0 && tid < (int)nclear) p.result[tid] = 0;
     if (blockIdx.x == 0 && tid == 0 && p.stale) *const_cast<u64 *>(p.stale) = 0;  // a fresh table: whatever a verification said about the old one is void
     if (wave < 2) {
-        const u64 t = wave == 0 ? c0 : c1;
-        u64 diag = t * (u64)tile_items;
-        if (diag > N) diag = N;
-        u64 lo = diag > p.nb ? diag - p.nb : 0;
-        u64 hi = diag < p.na ? diag : p.na;
-#if SETOP_PART_INTERP1
-        if (lo < hi) {
-            const u64 W = SETOP_PART_INTERP1;
-            u64 est = (u64)((double)diag * ((double)p.na / (double)N));
-            est = est < lo ? lo : (est > hi ? hi : est);
-            const u64 L = est > lo + W ? est - W : lo;
-            const u64 R = est + W < hi ? est + W : hi;
-            bool pl = true, pr = false;
-            if (L > lo) { const u64 j = diag - L; pl = key_le<RANK>(p.a[L - 1], RANK ? p.ra[L - 1] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-            if (R < hi) { const u64 j = diag - 1 - R; pr = key_le<RANK>(p.a[R], RANK ? p.ra[R] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-            if (L > lo) { if (pl) lo = L; else hi = L - 1; }
-            if (R < hi) { if (!pr) hi = R; else lo = R + 1; }
-        }
-#endif
-        while (lo < hi) {  // wave-uniform 64-ary search (see setop_partition_coop_kernel)
-            const u64 span = hi - lo;
-            const u64 cand = span <= 64 ? lo + (u64)lane
-                                        : lo + (span / 65) * (u64)(lane + 1) + ((span % 65) * (u64)(lane + 1)) / 65;
-            const bool active = cand < hi;
-            bool le = false;
-            if (active) {
-                const u64 j = diag - 1 - cand;
-                le = key_le<RANK>(p.a[cand], RANK ? p.ra[cand] : 0, p.b[j], RANK ? p.rb[j] : 0);
-            }
-            const u64 m_le = __ballot(le), m_act = __ballot(active);
-            const int n_true = __popcll(m_le), n_act = __popcll(m_act);
-            const u64 c_last_true = __shfl(cand, n_true > 0 ? n_true - 1 : 0, 64);
-            const u64 c_first_false = __shfl(cand, n_true < 64 ? n_true : 63, 64);
-            const u64 nlo = n_true > 0 ? c_last_true + 1 : lo;
-            const u64 nhi = n_true < n_act ? c_first_false : hi;
-            lo = nlo;
-            hi = nhi;
-        }
+        const u64 a = mp_split_wave<RANK>(p, wave == 0 ? c0 : c1, tile_items, lane);
         if (lane == 0) {
-            s_end[wave] = lo;
-            if (wave == 0) p.mp[c0] = lo;
-            else if (c1 == p.ntiles) p.mp[c1] = lo;  // the last boundary has no segment of its own
+            s_end[wave] = a;
+            if (wave == 0) p.mp[c0] = a;
+            else if (c1 == p.ntiles) p.mp[c1] = a;  // the last boundary has no segment of its own
         }
     }
     __syncthreads();
     const u64 t = c0 + (u64)tid;
     if (tid == 0 || tid >= PART_COARSE || t >= c1) return;
-    const u64 l0 = s_end[0], h0 = s_end[1];
-    u64 diag = t * (u64)tile_items;
-    if (diag > N) diag = N;
-    u64 lo = diag > p.nb ? diag - p.nb : 0;
-    u64 hi = diag < p.na ? diag : p.na;
-    lo = lo > l0 ? lo : l0;
-    hi = hi < h0 ? hi : h0;
-#if SETOP_PART_INTERP
-    if (lo < hi) {
-        const u64 W = SETOP_PART_INTERP;
-        u64 est = l0 + (h0 - l0) * (t - c0) / (c1 - c0);
-        est = est < lo ? lo : (est > hi ? hi : est);
-        const u64 L = est > lo + W ? est - W : lo;
-        const u64 R = est + W < hi ? est + W : hi;
-        bool pl = true, pr = false;
-        if (L > lo) { const u64 j = diag - L; pl = key_le<RANK>(p.a[L - 1], RANK ? p.ra[L - 1] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-        if (R < hi) { const u64 j = diag - 1 - R; pr = key_le<RANK>(p.a[R], RANK ? p.ra[R] : 0, p.b[j], RANK ? p.rb[j] : 0); }
-        if (L > lo) { if (pl) lo = L; else hi = L - 1; }
-        if (R < hi) { if (!pr) hi = R; else lo = R + 1; }
-    }
-#endif
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        const u64 j = diag - 1 - mid;
-        const bool le = key_le<RANK>(p.a[mid], RANK ? p.ra[mid] : 0, p.b[j], RANK ? p.rb[j] : 0);
-        if (le) lo = mid + 1; else hi = mid;
-    }
-    p.mp[t] = lo;
+    p.mp[t] = mp_split_between<RANK>(p, t, tile_items, c0, c1, s_end[0], s_end[1]);
 }
+
+// The slot's second column (ukm_ctx::PartCache): MP[t] = how many matched pairs have their A record in front of boundary t
+// (the merge loop attributes a match to its A step, peeking at B's halo) -- a property of the pair, not of the operation.
+// With the diagonal d_t, the split a_t (b_t = d_t - a_t) and s_t = [A[a_t - 1] == B[b_t]] (a matched pair that straddles the
+// boundary) the exclusive output offset of tile t is
+//     inter: MP[t]      diff: a_t - MP[t]      union: d_t - MP[t] + s_t   (the union drops a pair's B record, in B's tile)
+// forwards (setop_partition_verify_kernel) and backwards (setop_counts_record_kernel, from the look-back's prefixes):
+__device__ __forceinline__ u64 setop_offset_of(int op, u64 m, u64 a, u64 d, u64 s) {
+    return op == UKM_OP_INTER ? m : (op == UKM_OP_DIFF ? a - m : d - m + s);
+}
+__device__ __forceinline__ u64 setop_matches_of(int op, u64 e, u64 a, u64 d, u64 s) {
+    return op == UKM_OP_INTER ? e : (op == UKM_OP_DIFF ? a - e : d + s - e);
+}
+// A[ia] and B[ib] where the caller's test needs them (`in`).  Both loads are issued whatever `in` says -- clamped, harmless
+// indices where the test holds trivially -- so that all keys of a boundary are in flight together.
+struct MpKeys { u64 ka, kb; };
+__device__ __forceinline__ MpKeys mp_keys(const SetopArgs &p, bool in, u64 ia, u64 ib) { return {p.a[in ? ia : 0], p.b[in ? ib : 0]}; }
 
 // A hit of the partition cache: the table in p.mp was computed by the kernel above for the same (a, b, na, nb, tile_items),
 // but the buffers may have been rewritten since.  Searching again costs ~17 dependent round trips; CHECKING costs one:
@@ -353,26 +310,19 @@ __global__ __launch_bounds__(256) void setop_partition_fused_kernel(SetopArgs p,
 // kernel of the launch behind this one returns at its top (setop_table_stale).
 //
 // `counts` != nullptr: the launch behind this one takes its output offsets from the slot's second column instead of a
-// look-back.  counts[t] = MP[t] = how many matched pairs have their A record in front of boundary t (the merge loop
-// attributes a match to its A step, peeking at B's halo) -- a property of the pair, not of the operation.  With d_t and
-// a_t as above and s_t = [A[a_t - 1] == B[b_t]] (a matched pair that straddles the boundary; both keys are loaded for the
-// check anyway) the exclusive offset of tile t is
-//     inter: MP[t]      diff: a_t - MP[t]      union: d_t - MP[t] + s_t   (the union drops a pair's B record, in B's tile)
-// and p.base[0 .. ntiles] gets this operation's.  The column may hold anything too: MP[0] = 0 and every step within
-// 0 <= MP[t] - MP[t-1] <= a_t - a_{t-1}, or the table is stale -- which leaves 0 <= base[t] <= d_t + 1 for every operation.
-// The tile kernel then checks every tile's count against its step (FLAG_OFFS), so a table that merely belongs to other
-// contents costs a second pass, never a wrong result.  No status line is read by that launch: none is cleared.
+// look-back, and p.base[0 .. ntiles] gets this operation's (setop_offset_of; both keys of s_t are loaded for the check
+// anyway).  The column may hold anything too: MP[0] = 0 and every step within 0 <= MP[t] - MP[t-1] <= a_t - a_{t-1}, or the
+// table is stale -- which leaves 0 <= base[t] <= d_t + 1 for every operation.  The tile kernel then checks every tile's
+// count against its step (FLAG_OFFS), so a table that merely belongs to other contents costs a second pass, never a wrong
+// result.  No status line is read by that launch: none is cleared.
 __global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p, int tile_items, u32 nclear, const u64 *counts, int op) {
     const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < nclear) p.result[threadIdx.x] = 0;
     if (!counts && t < p.ntiles) p.status[t * LB_STRIDE] = 0;
     if (t > p.ntiles) return;
-    const u64 N = p.na + p.nb;
-    u64 d = t * (u64)tile_items;
-    if (d > N) d = N;
-    const u64 a = p.mp[t];
-    const u64 lo = d > p.nb ? d - p.nb : 0, hi = d < p.na ? d : p.na;
-    bool good = a >= lo && a <= hi;
+    const MpDiag g = mp_diag(p, t, tile_items);
+    const u64 d = g.diag, a = p.mp[t];
+    bool good = a >= g.lo && a <= g.hi;
     u64 ap = 0;
     if (good && t > 0) {
         // the tile in front of this boundary: 0 <= its A items <= its items (<= tile_items), which leaves its B items >= 0 too
@@ -388,39 +338,34 @@ __global__ __launch_bounds__(256) void setop_partition_verify_kernel(SetopArgs p
     }
     if (good) {
         const u64 b = d - a;  // <= nb by a >= lo
-        // (both loads of a test are issued whatever the other says: clamped, harmless indices where a half holds trivially)
         const bool t1 = a != 0 && b != p.nb, t2 = b != 0 && a != p.na;
-        const u64 a1 = p.a[t1 ? a - 1 : 0], b1 = p.b[t1 ? b : 0];
-        const u64 b2 = p.b[t2 ? b - 1 : 0], a2 = p.a[t2 ? a : 0];
-        good = (!t1 || a1 <= b1) && (!t2 || b2 < a2);
-        s = (t1 && a1 == b1) ? 1 : 0;
+        const MpKeys k1 = mp_keys(p, t1, a - 1, b), k2 = mp_keys(p, t2, a, b - 1);
+        good = (!t1 || k1.ka <= k1.kb) && (!t2 || k2.kb < k2.ka);
+        s = (t1 && k1.ka == k1.kb) ? 1 : 0;
     }
     if (!good) *const_cast<u64 *>(p.stale) = 1;  // (every writer writes the same value)
-    else if (counts) p.base[t] = op == UKM_OP_INTER ? m : (op == UKM_OP_DIFF ? a - m : d - m + s);
+    else if (counts) p.base[t] = setop_offset_of(op, m, a, d, s);
 }
 
 // Behind a plain-key pass that ran WITH the look-back on the slot's table: every status word now holds LB_INCL | the
-// inclusive prefix of its tile, i.e. the exclusive offset of the next one.  One thread per boundary turns that -- with the
-// formulas above read the other way -- into MP[t], the slot's second column.  The host declares the column valid only after
-// the read-back of this launch shows no flag; until then nothing reads it.  (A stale table: no tile has run, nothing to do.)
+// inclusive prefix of its tile, i.e. the exclusive offset of the next one.  One thread per boundary turns that into MP[t]
+// (setop_matches_of).  The host declares the column valid only after the read-back of this launch shows no flag; until
+// then nothing reads it.  (A stale table: no tile has run, nothing to do.)
 __global__ __launch_bounds__(256) void setop_counts_record_kernel(SetopArgs p, int tile_items, int op, u64 *counts) {
     const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
     if (t > p.ntiles || setop_table_stale(p)) return;
     u64 m = 0;
     if (t > 0) {
-        const u64 N = p.na + p.nb;
-        u64 d = t * (u64)tile_items;
-        if (d > N) d = N;
-        const u64 a = p.mp[t];
+        const u64 d = mp_diag(p, t, tile_items).diag, a = p.mp[t];
         const u64 e = lb_load(&p.status[(t - 1) * LB_STRIDE]) & LB_VAL;
-        if (op == UKM_OP_INTER) m = e;
-        else if (op == UKM_OP_DIFF) m = a - e;
-        else {
+        u64 s = 0;
+        if (op == UKM_OP_UNION) {  // (the only operation whose offsets have the straddle term)
             const u64 b = d - a;
             const bool t1 = a != 0 && a <= p.na && b < p.nb;  // (a fresh or verified table: always in range)
-            const u64 a1 = p.a[t1 ? a - 1 : 0], b1 = p.b[t1 ? b : 0];
-            m = d + ((t1 && a1 == b1) ? 1 : 0) - e;
+            const MpKeys k1 = mp_keys(p, t1, a - 1, b);
+            s = (t1 && k1.ka == k1.kb) ? 1 : 0;
         }
+        m = setop_matches_of(op, e, a, d, s);
     }
     counts[t] = m;
 }
@@ -1474,6 +1419,58 @@ constexpr int VT_PLAIN = SETOP_VT;  // 19 items per thread: 76 KiB of keys in LD
 constexpr int VT_TAX = SETOP_VT_TAX;
 constexpr int VT_RANK = 12;  // ranks ride along (the multiset re-run), with or without taxids
 
+// what a pass and a chained link (na = the bound, the link adds na_dev) hand to their kernels, less the control block
+SetopArgs setop_args(ukm_ctx *c, const u64 *a, const u32 *ta, const u32 *ra, u64 na, const u64 *b, const u32 *tb, const u32 *rb, u64 nb,
+                     u64 tile_items, u32 flags, u64 *out, u32 *tout, u64 out_cap, u32 cta, u32 ctb) {
+    SetopArgs p;
+    memset(&p, 0, sizeof(p));
+    p.a = a; p.b = b; p.ta = ta; p.tb = tb; p.ra = ra; p.rb = rb;
+    p.na = na; p.nb = nb;
+    p.out = out; p.tout = tout; p.out_cap = out_cap;
+    p.ntiles = (na + nb + tile_items - 1) / tile_items;
+    p.tax = ukm_taxdev(c);
+    p.flags = flags;
+    p.cta = cta;
+    p.ctb = ctb;
+    return p;
+}
+
+// The partition launch(es) that fill p.mp.  FUSED also zeroes the control block and the status lines (and p.stale's word);
+// SINGLE clears p.zero_status status lines; TWO_LEVEL clears nothing.
+enum class PartKernels { FUSED, TWO_LEVEL, SINGLE };
+template <bool RANK>
+void launch_partition_as(hipStream_t st, const SetopArgs &p, int tile_items, PartKernels which) {
+    const dim3 wg(256);
+    const auto blocks = [](u64 items, u64 per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); };
+    if (which == PartKernels::FUSED) {  // a workgroup per coarse segment
+        hipLaunchKernelGGL((setop_partition_fused_kernel<RANK>), blocks(p.ntiles, PART_COARSE), wg, 0, st, p, tile_items, (u32)LbCtl::HEAD);
+    } else if (which == PartKernels::TWO_LEVEL) {  // a wave per coarse boundary (four to a workgroup), then a thread per boundary
+        hipLaunchKernelGGL((setop_partition_wave_kernel<RANK, true>), blocks(p.ntiles / PART_COARSE + 2, 4), wg, 0, st, p, tile_items);
+        hipLaunchKernelGGL((setop_partition_fine_kernel<RANK>), blocks(p.ntiles + 1, 256), wg, 0, st, p, tile_items);
+    } else {  // a wave per boundary
+        hipLaunchKernelGGL((setop_partition_wave_kernel<RANK, false>), blocks(p.ntiles + 1, 4), wg, 0, st, p, tile_items);
+    }
+}
+int launch_partition(ukm_ctx *c, const SetopArgs &p, u64 tile_items, bool rank, PartKernels which) {
+    if (rank) launch_partition_as<true>(c->stream, p, (int)tile_items, which);
+    else launch_partition_as<false>(c->stream, p, (int)tile_items, which);
+    UKM_HIP(hipGetLastError());
+    return UKM_OK;
+}
+
+// How a pass gets its merge-path table and its tiles' output offsets, and what it does about the slot's match counts
+// (DESIGN.md section 4.1 has the table of cases).  Chosen once; only the two downgrades in run_setop_pass change it.
+enum class Plan {
+    SEARCH,           // a partition launch fills the table; offsets by look-back
+    VERIFY_LOOKBACK,  // the cached table, verified; offsets by look-back
+    VERIFY_TABLE,     // the cached table and counts, verified; offsets from the counts (TABLE tiles, no look-back)
+};
+enum class Counts {
+    NONE,    // the pass leaves no valid counts in the slot
+    KEPT,    // the slot's counts are valid and stay (VERIFY_TABLE: and are used)
+    RECORD,  // setop_counts_record_kernel writes them behind the look-back
+};
+
 // One pass of the tiled set operation.  result_host[0] = total, [1] = flags.
 // (cta, ctb): the file taxid of a stream whose ta / tb is null (SetopArgs); tax && !ta && !tb = the CT instantiation
 // may_cache: a and b are the caller's own device buffers (the public 2-way entry): the pass may take its merge-path table
@@ -1500,17 +1497,7 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     const bool tax_stream = tax && !rank && op == UKM_OP_DIFF && !(flags & UKM_F_CMP_TAXID);
     const int vt = rank ? VT_RANK : (tax ? (tax_stream ? VT_RANK : VT_TAX) : VT_PLAIN);
     const u64 tile_items = (u64)NTS * vt;
-    const u64 N = na + nb;
-    SetopArgs p;
-    memset(&p, 0, sizeof(p));
-    p.a = a; p.b = b; p.ta = ta; p.tb = tb; p.ra = ra; p.rb = rb;
-    p.na = na; p.nb = nb;
-    p.out = out; p.tout = tout; p.out_cap = out_cap;
-    p.ntiles = (N + tile_items - 1) / tile_items;
-    p.tax = ukm_taxdev(c);
-    p.flags = flags;
-    p.cta = cta;
-    p.ctb = ctb;
+    SetopArgs p = setop_args(c, a, ta, ra, na, b, tb, rb, nb, tile_items, flags, out, tout, out_cap, cta, ctb);
     if (p.ntiles > 0xFFFFFFFFull) UKM_FAIL(UKM_ERR_INVALID, "setop: input too large");
 
     LbCtl blk;  // the partition points behind it
@@ -1529,80 +1516,47 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
 #endif
     // The partition points (they survive a repeated launch).  A plain call takes the fused kernel, which also zeroes
     // the control block for the first attempt.
-    const bool fused = !ukm_env_is(c, "UKM_SETOP_FUSED_PART", '0') && p.ntiles >= 4 * PART_COARSE;  // (developer knob)
+    const bool two_level = p.ntiles >= 4 * PART_COARSE;
+    const bool fused = two_level && !ukm_env_is(c, "UKM_SETOP_FUSED_PART", '0');  // (developer knob)
     // The partition cache (ukm_ctx::PartCache): only where the fused kernel would run -- below 4 * PART_COARSE tiles the
     // partition is a 12 us kernel --, never with ranks (the multiset re-run), never on a chained link (sizes on the device:
     // another entry point).  UKM_SETOP_PART_REUSE=0 (developer knob) turns it off.
     ukm_ctx::PartCache &pc = c->part_cache;
-    bool cache = may_cache && fused && !rank && na && nb && !pc.off && !ukm_env_is(c, "UKM_SETOP_PART_REUSE", '0');
-    bool hit = false;
+    const ukm_ctx::PartCache::Key key = {a, b, na, nb, tile_items};
+    const bool cache = may_cache && fused && !rank && na && nb && !pc.off && !ukm_env_is(c, "UKM_SETOP_PART_REUSE", '0') && pc.reserve(p.ntiles);
+    // The match counts MP of the slot (its second column; setop_offset_of has the formulas): a plain-key union / inter /
+    // diff that hits the partition cache while they are valid takes its tiles' output offsets from them -- the TABLE
+    // instantiation, no look-back -- and every other such pass on the slot's table records them behind its look-back.
+    // UKM_SETOP_OFFS_REUSE=0 turns both off; UKM_SETOP_OFFS_OPS (developer knob) = which operations use the counts,
+    // 1 << op each (profiles/offs_reuse_notes.md has the measurements behind the default).
+    const bool plain3 = !tax && !ct && !rank && (op == UKM_OP_UNION || op == UKM_OP_INTER || op == UKM_OP_DIFF);
+    const bool offs_on = cache && plain3 && !pc.offs_off && !ukm_env_is(c, "UKM_SETOP_OFFS_REUSE", '0');
+    Plan plan = Plan::SEARCH;
+    Counts counts = offs_on ? Counts::RECORD : Counts::NONE;
     if (cache) {
-        // (the table and, behind it, the match counts: PartCache)
-        const size_t need = ukm_ctx::PartCache::PC_HEAD + 2 * ((size_t)p.ntiles + 1);
-        if (pc.cap_words < need) {  // grown on demand; the slot's table goes with the old buffer
-            if (pc.buf) (void)hipFree(pc.buf);
-            pc.buf = nullptr;
-            pc.cap_words = 0;
-            pc.valid = false;
-            pc.counts_valid = false;
-            void *nb_ = nullptr;
-            if (hipMalloc(&nb_, need * sizeof(u64)) == hipSuccess) {
-                pc.buf = (u64 *)nb_;
-                pc.cap_words = need;
-            } else {
-                (void)hipGetLastError();  // no room for a cache: the call goes on without one
-                cache = false;
+        const ukm_ctx::PartCache::Opened slot = pc.open(key);
+        p.stale = pc.stale_word();
+        p.mp = pc.table();
+        if (slot.hit) {
+            plan = Plan::VERIFY_LOOKBACK;
+            if (slot.counts) {  // the column still belongs to the table this pass works on
+                counts = Counts::KEPT;
+                if (offs_on && ((ukm_env_int(c, "UKM_SETOP_OFFS_OPS", SETOP_OFFS_OPS) >> op) & 1) != 0) plan = Plan::VERIFY_TABLE;
             }
         }
     }
-    if (cache) {
-        hit = pc.valid && pc.a == a && pc.b == b && pc.na == na && pc.nb == nb && pc.tile_items == tile_items;
-        pc.valid = false;  // until this pass has come back: an error on the way leaves no key behind
-        p.stale = pc.buf;
-        p.mp = pc.buf + ukm_ctx::PartCache::PC_HEAD;
-    }
-    // The match counts MP of the slot (its second column; setop_partition_verify_kernel has the formulas): a plain-key
-    // union / inter / diff that hits the partition cache while they are valid takes its tiles' output offsets from them --
-    // the TABLE instantiation, no look-back -- and every other such pass on the slot's table records them behind its
-    // look-back.  UKM_SETOP_OFFS_REUSE=0 turns both off; UKM_SETOP_OFFS_OPS (developer knob) = which operations use the
-    // counts, 1 << op each (profiles/offs_reuse_notes.md has the measurements behind the default).
-    const bool plain3 = !tax && !ct && !rank && (op == UKM_OP_UNION || op == UKM_OP_INTER || op == UKM_OP_DIFF);
-    const bool offs_on = cache && plain3 && !pc.offs_off && !ukm_env_is(c, "UKM_SETOP_OFFS_REUSE", '0');
-    u64 *const counts = cache ? p.mp + p.ntiles + 1 : nullptr;
-    bool counts_good = cache && hit && pc.counts_valid;  // the column still belongs to the table this pass works on
-    if (cache) pc.counts_valid = false;                   // (like `valid`: until this pass has come back)
-    bool table = offs_on && counts_good && ((ukm_env_int(c, "UKM_SETOP_OFFS_OPS", SETOP_OFFS_OPS) >> op) & 1) != 0;
-    bool recorded = false;
-    if (hit) {
-        const unsigned vblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
-        p.base = blk.tail;  // (the arena's table words, which p.mp does not occupy on a cached pass)
-        hipLaunchKernelGGL(setop_partition_verify_kernel, dim3(vblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD,
-                           table ? (const u64 *)counts : (const u64 *)nullptr, op);
-        UKM_HIP(hipGetLastError());
-    } else if (fused) {
-        const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
-        if (rank) hipLaunchKernelGGL((setop_partition_fused_kernel<true>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
-        else hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
-        UKM_HIP(hipGetLastError());
-    } else if (p.ntiles >= 4 * PART_COARSE) {
-        const unsigned cblocks = (unsigned)((p.ntiles / PART_COARSE + 2 + 3) / 4);  // one wave per coarse boundary
-        const unsigned pblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
-        if (rank) {
-            hipLaunchKernelGGL((setop_partition_coop_kernel<true, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-            hipLaunchKernelGGL((setop_partition_kernel<true, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-        } else {
-            hipLaunchKernelGGL((setop_partition_coop_kernel<false, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-            hipLaunchKernelGGL((setop_partition_kernel<false, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-        }
+    if (plan == Plan::SEARCH) {
+        UKM_TRY(launch_partition(c, p, tile_items, rank, fused ? PartKernels::FUSED : (two_level ? PartKernels::TWO_LEVEL : PartKernels::SINGLE)));
     } else {
-        const unsigned wblocks = (unsigned)((p.ntiles + 1 + 3) / 4);  // one wave per boundary
-        if (rank) hipLaunchKernelGGL((setop_partition_coop_kernel<true, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-        else hipLaunchKernelGGL((setop_partition_coop_kernel<false, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
+        p.base = blk.tail;  // (the arena's table words, which p.mp does not occupy on a cached pass)
+        hipLaunchKernelGGL(setop_partition_verify_kernel, dim3((unsigned)((p.ntiles + 1 + 255) / 256)), dim3(256), 0, c->stream, p, (int)tile_items,
+                           (u32)LbCtl::HEAD, plan == Plan::VERIFY_TABLE ? (const u64 *)pc.counts(p.ntiles) : (const u64 *)nullptr, op);
+        UKM_HIP(hipGetLastError());
     }
     // (the bracket holds the tile kernel with its CT / fix / gather kernels, not the partition)
     const LbLaunch how = {"setop", "set-op kernel", FLAG_TIMEOUT, true, false, fused};
     const auto launch_tiles = [&](bool ticket) {
-        if (table) {
+        if (plan == Plan::VERIFY_TABLE) {
             launch_table<NTS, VT_PLAIN>(op, p, c->stream);
         } else if (rank) {
             if (tax) launch_op<true, true, NTS, VT_RANK>(op, p, c->stream, ticket);
@@ -1616,59 +1570,54 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
             else if (ct) launch_op<false, false, NTS, VT_PLAIN, true>(op, p, c->stream, ticket);
             else launch_op<false, false, NTS, VT_PLAIN>(op, p, c->stream, ticket);
         }
-        if (offs_on && !table && !counts_good) {
-            hipLaunchKernelGGL(setop_counts_record_kernel, dim3((unsigned)((p.ntiles + 1 + 255) / 256)), dim3(256), 0, c->stream, p, (int)tile_items, op, counts);
-            recorded = true;
-        }
+        if (counts == Counts::RECORD)
+            hipLaunchKernelGGL(setop_counts_record_kernel, dim3((unsigned)((p.ntiles + 1 + 255) / 256)), dim3(256), 0, c->stream, p, (int)tile_items, op, pc.counts(p.ntiles));
         if (p.stale) hipLaunchKernelGGL(setop_stale_report_kernel, dim3(1), dim3(1), 0, c->stream, p);
         return UKM_OK;
     };
     UKM_TRY(ukm_lb_launch(c, blk, how, launch_tiles, result_host));
-    if (hit) {
-        if (result_host[1] & FLAG_STALE) {
-            // The buffers were rewritten under the key.  No tile has run (the other flags of that pass mean nothing): the
-            // search after all -- its kernel clears the stale word and the control block -- and the launch again, once.
+    // The two downgrades, each taken once at the most.
+    if (plan != Plan::SEARCH) {
+        const bool stale = (result_host[1] & FLAG_STALE) != 0;
+        pc.note_table(stale);
+        if (stale) {
+            // VERIFY_* -> SEARCH.  The buffers were rewritten under the key.  No tile has run (the other flags of that pass mean
+            // nothing): the search after all -- the fused kernel, which clears the stale word and the control block; without
+            // ranks, which the cache excludes -- and the launch again.  The counts go with the table: this pass records fresh ones.
             c->stat_setop_part_stale++;
-            if (++pc.stale_run >= 2) pc.off = true;
-            table = false;  // the counts go with the table: this pass records fresh ones
-            counts_good = false;
-            const unsigned sblocks = (unsigned)((p.ntiles + PART_COARSE - 1) / PART_COARSE);
-            hipLaunchKernelGGL((setop_partition_fused_kernel<false>), dim3(sblocks), dim3(256), 0, c->stream, p, (int)tile_items, (u32)LbCtl::HEAD);
-            UKM_HIP(hipGetLastError());
+            plan = Plan::SEARCH;
+            counts = offs_on ? Counts::RECORD : Counts::NONE;
+            UKM_TRY(launch_partition(c, p, tile_items, rank, PartKernels::FUSED));
             UKM_TRY(ukm_lb_launch(c, blk, how, launch_tiles, result_host));
         } else {
             c->stat_setop_part_hits++;
-            pc.stale_run = 0;
-            if (table) {
-                const u64 fl = result_host[1];
-                if ((fl & FLAG_OFFS) && !(fl & (FLAG_DUP | FLAG_UNSORTED))) {
-                    // The contents changed in place under an intact partition: some tile counted another number of records
-                    // than its step.  The output is void; the pass again, once, with the look-back (cleared control block and
-                    // status lines: the verification cleared no status line) -- which records fresh counts.
-                    c->stat_setop_offs_stale++;
-                    if (++pc.offs_stale_run >= 2) pc.offs_off = true;
-                    table = false;
-                    counts_good = false;
-                    LbLaunch again = how;
-                    again.first_zeroed = false;
-                    UKM_TRY(ukm_lb_launch(c, blk, again, launch_tiles, result_host));
-                } else if (!(fl & FLAG_OFFS)) {
-                    c->stat_setop_offs_hits++;
-                    pc.offs_stale_run = 0;
-                }
-                // (duplicates or disorder beside FLAG_OFFS: the caller discards this pass anyway -- no second one)
-                if (result_host[1] & FLAG_OFFS) counts_good = false;
-                result_host[1] &= ~(u64)FLAG_OFFS;
-            }
         }
     }
-    if (result_host[1] & FLAG_STALE) UKM_FAIL(UKM_ERR_HIP, "setop: a fresh partition table failed its verification");
-    if (cache) {  // the table in the slot belongs to this pass's inputs as they were a moment ago
-        pc.a = a; pc.b = b; pc.na = na; pc.nb = nb; pc.tile_items = tile_items;
-        pc.valid = true;
-        // the counts: kept or freshly recorded, and only behind a pass that came back with no flag at all
-        pc.counts_valid = (counts_good || recorded) && result_host[1] == 0;
+    if (plan == Plan::VERIFY_TABLE) {
+        const u64 fl = result_host[1];
+        if (!(fl & FLAG_OFFS)) {
+            c->stat_setop_offs_hits++;
+            pc.note_counts(false);
+        } else if (!(fl & (FLAG_DUP | FLAG_UNSORTED))) {
+            // VERIFY_TABLE -> VERIFY_LOOKBACK, on the same (verified) table.  The contents changed in place under an intact
+            // partition: some tile counted another number of records than its step.  The output is void; the pass again with
+            // the look-back (cleared control block and status lines: the verification cleared no status line) -- which
+            // records fresh counts.
+            c->stat_setop_offs_stale++;
+            pc.note_counts(true);
+            plan = Plan::VERIFY_LOOKBACK;
+            counts = Counts::RECORD;
+            LbLaunch again = how;
+            again.first_zeroed = false;
+            UKM_TRY(ukm_lb_launch(c, blk, again, launch_tiles, result_host));
+        } else {
+            counts = Counts::NONE;  // duplicates or disorder beside FLAG_OFFS: the caller discards this pass anyway -- no second one
+        }
+        result_host[1] &= ~(u64)FLAG_OFFS;
     }
+    if (result_host[1] & FLAG_STALE) UKM_FAIL(UKM_ERR_HIP, "setop: a fresh partition table failed its verification");
+    // the counts: kept or freshly recorded, and only behind a pass that came back with no flag at all
+    if (cache) pc.commit(key, counts != Counts::NONE && result_host[1] == 0);
 #ifdef UKM_PROFILE_PHASES
     {
         std::vector<u64> h((size_t)p.ntiles * 8);
@@ -1698,22 +1647,13 @@ int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_
     if (ct) tax = false;
     const int vt = tax ? VT_TAX : VT_PLAIN;
     const u64 tile_items = (u64)NTS * vt;
-    SetopArgs p;
-    memset(&p, 0, sizeof(p));
-    p.a = a; p.b = b; p.ta = ta; p.tb = tb;
-    p.na = na_max; p.nb = nb; p.na_dev = na_dev;
-    p.out = out; p.tout = tout; p.out_cap = out_cap;
-    p.ntiles = (na_max + nb + tile_items - 1) / tile_items;
-    p.tax = ukm_taxdev(c);
-    p.flags = flags;
-    p.cta = cta;
-    p.ctb = ctb;
+    SetopArgs p = setop_args(c, a, ta, nullptr, na_max, b, tb, nullptr, nb, tile_items, flags, out, tout, out_cap, cta, ctb);
+    p.na_dev = na_dev;
     if (p.ntiles == 0) return UKM_OK;
-    const unsigned pblocks = (unsigned)((p.ntiles + 1 + 255) / 256);
 #ifndef SETOP_LINK_SMALL_TILES
 #define SETOP_LINK_SMALL_TILES 2048
 #endif
-    // links of up to a few thousand tiles: ONE wave-cooperative partition kernel that also clears the status lines
+    // links of up to a few thousand tiles: ONE partition kernel (a wave per boundary) that also clears the status lines
     // (three launches less per link than memset + two-level partition; a 1000-file fold is launch bound)
     const bool small = p.ntiles < SETOP_LINK_SMALL_TILES;
     LbCtl blk;  // the head is the caller's; one status line more than tiles, the partition points behind them
@@ -1724,14 +1664,7 @@ int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_
     p.ticket = blk.ticket;
     p.status = blk.status;
     p.mp = blk.tail;
-    if (!small) {
-        const unsigned cblocks = (unsigned)((p.ntiles / PART_COARSE + 2 + 3) / 4);  // one wave per coarse boundary
-        hipLaunchKernelGGL((setop_partition_coop_kernel<false, 1>), dim3(cblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-        hipLaunchKernelGGL((setop_partition_kernel<false, 2>), dim3(pblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-    } else {
-        const unsigned wblocks = (unsigned)((p.ntiles + 1 + 3) / 4);  // one wave per boundary
-        hipLaunchKernelGGL((setop_partition_coop_kernel<false, 0>), dim3(wblocks), dim3(256), 0, c->stream, p, (int)tile_items);
-    }
+    UKM_TRY(launch_partition(c, p, tile_items, false, small ? PartKernels::SINGLE : PartKernels::TWO_LEVEL));
     if (tax) launch_op<true, false, NTS, VT_TAX>(op, p, c->stream, c->setop_force_ticket);
     else if (ct) launch_op<false, false, NTS, VT_PLAIN, true>(op, p, c->stream, c->setop_force_ticket);
     else {
