@@ -273,6 +273,38 @@ int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_
             uint64_t min_len, uint32_t *out_rec, uint64_t *out_start, uint64_t *out_end, uint64_t out_cap,
             uint64_t *n_out);
 
+/* ---- ukm_map_gapped: `unikmer map` with -x / -X / --circular (map.go:298-490).  Arguments, contracts, errors and the
+ *      option "map_sorted" are ukm_map's; max_gap_size = -x, max_gap_num = -X.  Per record of L >= k bases every window
+ *      has one of three classes: G its code is in the set and (allow_multi, or it occurs once among the windows of its
+ *      genome); B in the set but multiple-mapped (never with allow_multi); M not in the set.  Linear records: the STREAM is
+ *      the record's L - k + 1 windows.  circular: the classes are those of the record's L circular windows (multiplicity is
+ *      counted among exactly these, map.go:222-226) and the stream has 2L - k + 1 positions, position i with the class of
+ *      circular window i mod L (the reference maps the record written twice, map.go:338-340).
+ *        1. RUNS are the maximal stretches of G inside one record's stream.
+ *        2. The separator in front of a run is SOFT when it consists of M only and is at most max_gap_size long; HARD when
+ *           it contains a B, is longer, or the run is the first of its record.  A CHAIN is a maximal sequence of runs
+ *           joined by soft separators.
+ *        3. With the runs of a chain numbered from 0 and X = max_gap_num, a REGION is the group of runs
+ *           [j(X + 1), j(X + 1) + X], cut at the chain's end: start = first window of the group's first run, last = last
+ *           window of its last run.  The small gap behind a full group belongs to no region.
+ *        4. A region is kept when last - start + k >= min_len.  Linear: (rec, start, last + k).  circular: regions with
+ *           start >= L are dropped (map.go:407/423); the end is start + L when last - start + k > L (map.go:381), else
+ *           last + k, and may exceed L.
+ *        5. Output in record order, then start order.  max_gap_size = 0 ignores max_gap_num (the reference warns and
+ *           ignores); max_gap_size = 0 with circular = 0 is exactly ukm_map.
+ *      Two deliberate deviations from map.go: `flag`, `lastGapNum` and `lastmatch` start every
+ *      record as they start the first one (the reference carries them over, and a record that ends inside a tolerated gap
+ *      makes the next records lose every region up to their first hard break); after the circular `break` nothing more is
+ *      emitted for the record (the reference prints a stale region shorter than k, visible only when min_len < k).
+ *      UKM_ERR_INVALID: max_gap_size > 0 with max_gap_num = 0 (map.go:112); either gap value above 2^31 - 1; min_len < 1;
+ *      2^31 or more stream positions in one call whenever gaps or circular are asked for (run and break counts share one
+ *      look-back word): split the records over several calls.  UKM_ERR_CAPACITY: *n_out = the exact number of regions,
+ *      nothing is written behind out_cap. */
+int ukm_map_gapped(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
+                   uint64_t n_genome, int k, int hashed, int circular, const uint64_t *set_keys, uint64_t n_set,
+                   int allow_multi, uint64_t min_len, uint64_t max_gap_size, uint64_t max_gap_num, uint32_t *out_rec,
+                   uint64_t *out_start, uint64_t *out_end, uint64_t out_cap, uint64_t *n_out);
+
 /* ---- sorts: replace sortutil.Uint64s (count.go:581, union.go:274,295, sort.go:463 ...) and
  *      sorts.Quicksort(CodeTaxidSlice) (sort.go:268,331,457).  In place, ascending by code;
  *      pairs are sorted by code only, stably.  key_bits = number of significant low bits

@@ -12,13 +12,18 @@
 //                 beyond L2 is 64 scattered rows per wave).  It writes one flag byte per window and/or compacts the
 //                 hits, in window order, with the library's look-back.
 //   ukm_map       flags -> (without allow_multi: the HITS alone are compacted as (code, window), sorted by code with
-//                 ukm_dev_sort, and classify_kernel clears the flag of every hit whose sorted neighbour carries the same
+//                 ukm_dev_sort, and classify_kernel takes the good bit from every hit whose sorted neighbour carries the same
 //                 code in the same genome: all occurrences of a code hit together, so counting among the hits is counting
 //                 among all windows; a set that covers little of the genome sorts little) -> mark_rec_kernel raises the
 //                 "first window of a record" bit -> runs_kernel finds run starts and ends in one pass (the j-th start and
 //                 the j-th end belong together: an end's slot is the number of starts up to it minus one, so ONE look-back
 //                 over the start counts orders both) -> emit_kernel keeps the runs of at least min_len bases, compacted in
 //                 order.
+//   ukm_map_gapped  map.go:298-490 with -x / -X / --circular (definition: include/unikmer_hip.h): the same classes, a
+//                 multiple-mapped hit marked F_MULTI; circular records: unroll_kernel writes the class bytes of the L
+//                 circular windows out as the 2L - k + 1 positions of the record written twice; runs_kernel<GAPPED> also
+//                 counts breaks (multiple-mapped positions, record starts) in its look-back word; chain_kernel joins runs
+//                 across small gaps without a break; emit_gapped_kernel emits every group of max_gap_num + 1 runs of a chain.
 //   ukm_locate    the queries are sorted stably with their indices (a code's first copy comes first, and the directory's
 //                 lower bound finds exactly it); the join emits (index of that query, window) per hit in window order;
 //                 a stable sort by query index is then the reference's output order, and expand_kernel turns window
@@ -40,7 +45,9 @@ constexpr int NT = 256;
 constexpr int VT = 8;            // consecutive windows per thread: their eight flag bytes are one 8-byte word
 constexpr int TILE = NT * VT;
 enum : u64 { MAP_FLAG_TIMEOUT = 4 };  // result word [1]
-enum : u32 { F_GOOD = 1, F_REC = 2 }; // flag byte of a window: good / first window of its record
+// flag byte of a window: good / first window of its record / in the set but multiple-mapped (ukm_map_gapped's class B;
+// ukm_map reads F_GOOD alone, so a multiple-mapped hit is a miss to it)
+enum : u32 { F_GOOD = 1, F_REC = 2, F_MULTI = 4 };
 
 // first index in [0, n) with a[i] > x
 __device__ __forceinline__ u64 upper_bound_u64(const u64 *a, u64 n, u64 x) {
@@ -135,10 +142,10 @@ __device__ __forceinline__ bool multi_mapped(const u64 *hk, const u32 *hv, u64 n
     if (j > 0 && hk[j - 1] == code && same_genome(g, hv[j - 1], w)) return true;
     return j + 1 < n && hk[j + 1] == code && same_genome(g, w, hv[j + 1]);
 }
-// the hits alone, sorted: clear the flag of the multiple-mapped ones
+// the hits alone, sorted: the multiple-mapped ones are no longer good
 __global__ void classify_kernel(const u64 *hk, const u32 *hv, u64 n, Genomes g, u8 *flag) {
     const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n && multi_mapped(hk, hv, n, j, g)) flag[hv[j]] = 0;
+    if (j < n && multi_mapped(hk, hv, n, j, g)) flag[hv[j]] = (u8)F_MULTI;
 }
 // option map_sorted: ALL windows sorted; membership in sorted order, every flag scattered back
 __global__ void sorted_classify_kernel(const u64 *hk, const u32 *hv, u64 n, Dir d, Genomes g, int allow_multi, u8 *flag) {
@@ -146,9 +153,9 @@ __global__ void sorted_classify_kernel(const u64 *hk, const u32 *hv, u64 n, Dir 
     if (j >= n) return;
     const u64 code = hk[j];
     const u32 lb = dir_lower_bound(d, code);
-    bool good = (u64)lb < d.n && d.keys[lb] == code;
-    if (good && !allow_multi) good = !multi_mapped(hk, hv, n, j, g);
-    flag[hv[j]] = good ? (u8)F_GOOD : (u8)0;
+    const bool hit = (u64)lb < d.n && d.keys[lb] == code;
+    const bool multi = hit && !allow_multi && multi_mapped(hk, hv, n, j, g);
+    flag[hv[j]] = !hit ? (u8)0 : multi ? (u8)F_MULTI : (u8)F_GOOD;
 }
 
 __global__ void mark_rec_kernel(const u64 *win_off, u64 n_rec, u8 *flag) {
@@ -161,6 +168,7 @@ struct RunArgs {
     const u8 *flag;  // whole 8-byte words, zero behind n
     u64 n;
     u32 *start, *end;  // [cap] first / last window of every run
+    u32 *brk;          // (GAPPED) [cap] breaks up to and including every run's first position
     u64 cap;
     u64 *status;
     u32 *ticket;
@@ -168,7 +176,13 @@ struct RunArgs {
     u64 ntiles;
 };
 
-template <bool TICKET>
+// GAPPED (ukm_map_gapped): the running count of BREAKS -- positions that are multiple-mapped (F_MULTI) or the first of
+// their record (F_REC) -- rides in the same look-back word, run starts in bits [30:0], breaks in [61:31] (fewer than
+// 2^31 positions per call, so neither field overflows), and every run keeps the count at its first position.  No break
+// lies inside a run behind that position (a good window is not multiple-mapped, a record's first window starts a run),
+// so the count at a run's end is the same number: two neighbouring runs have a break between them exactly when their
+// counts differ, whatever the length of the gap.
+template <bool TICKET, bool GAPPED>
 __global__ __launch_bounds__(NT) void runs_kernel(RunArgs p) {
     __shared__ u32 s_scan[NT / 64 + 1];
     __shared__ u64 s_misc[2];
@@ -179,7 +193,7 @@ __global__ __launch_bounds__(NT) void runs_kernel(RunArgs p) {
     const u64 f8 = in ? *reinterpret_cast<const u64 *>(p.flag + i0) : 0;
     u32 prev = (in && i0 > 0) ? p.flag[i0 - 1] : 0;
     const u32 next = (i0 + VT < p.n) ? p.flag[i0 + VT] : 0;
-    u32 starts = 0, ends = 0;
+    u32 starts = 0, ends = 0, brks = 0;
 #pragma unroll
     for (int s = 0; s < VT; s++) {
         const u32 f = (u32)(f8 >> (8 * s)) & 0xFFu;
@@ -187,22 +201,30 @@ __global__ __launch_bounds__(NT) void runs_kernel(RunArgs p) {
         const bool good = (f & F_GOOD) != 0;
         if (good && ((f & F_REC) || !(prev & F_GOOD))) starts |= 1u << s;
         if (good && (!(nf & F_GOOD) || (nf & F_REC))) ends |= 1u << s;
+        if (GAPPED && (f & (F_MULTI | F_REC))) brks |= 1u << s;
         prev = f;
     }
+    // (one block scan for both counts: at most 2048 of either per tile)
     u32 tot;
-    const u32 excl = block_excl_scan_u32<NT>((u32)__popc(starts), s_scan, &tot);
-    const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tot, &p.result[1], MAP_FLAG_TIMEOUT, &s_misc[1], tid, lane);
-    u64 slot = base + excl;  // runs that started in front of this thread's windows
+    const u32 excl = block_excl_scan_u32<NT>((u32)__popc(starts) | (GAPPED ? (u32)__popc(brks) << 16 : 0u), s_scan, &tot);
+    const u64 agg = GAPPED ? ((u64)(tot >> 16) << 31) | (u64)(tot & 0xFFFFu) : (u64)tot;
+    const u64 base = lb_tile_base<TICKET>(p.status, tile, agg, &p.result[1], MAP_FLAG_TIMEOUT, &s_misc[1], tid, lane);
+    u64 slot = (GAPPED ? base & 0x7FFFFFFFull : base) + (GAPPED ? excl & 0xFFFFu : excl);  // runs that started in front of this thread's windows
+    u32 nb = GAPPED ? (u32)(base >> 31) + (excl >> 16) : 0u;                                 // breaks in front of them
 #pragma unroll
     for (int s = 0; s < VT; s++) {
+        if (GAPPED) nb += (brks >> s) & 1u;
         if ((starts >> s) & 1u) {
-            if (slot < p.cap) p.start[slot] = (u32)(i0 + s);
+            if (slot < p.cap) {
+                p.start[slot] = (u32)(i0 + s);
+                if (GAPPED) p.brk[slot] = nb;
+            }
             slot++;
         }
         // an end closes the most recent start: slot - 1 (>= 0: a good window has a start at or in front of it)
         if (((ends >> s) & 1u) && slot >= 1 && slot - 1 < p.cap) p.end[slot - 1] = (u32)(i0 + s);
     }
-    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tot;
+    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = (GAPPED ? (base + agg) & 0x7FFFFFFFull : base + agg);
 }
 
 struct EmitArgs {
@@ -246,6 +268,140 @@ __global__ __launch_bounds__(NT) void emit_kernel(EmitArgs p) {
         p.out_rec[pos] = (u32)r;
         p.out_start[pos] = s - w0;
         p.out_end[pos] = e - w0 + (u64)p.k;
+    }
+    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tot;
+}
+
+// ---- ukm_map_gapped: the stream of a circular record, chains of runs, regions -------------------------------------------
+// A record of L >= k bases has 2L - k + 1 stream positions when circular (the windows of the record written twice,
+// map.go:338-340), none when it is shorter than k.
+__global__ void stream_count_kernel(const u64 *rec_off, u64 n_rec, int k, u64 *cnt) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_rec) return;
+    const u64 len = r < n_rec ? rec_off[r + 1] - rec_off[r] : 0;
+    cnt[r] = len < (u64)k ? 0 : 2 * len - (u64)k + 1;
+}
+
+// Class bytes of the circular windows (cls, L per record at win_off) -> flag bytes of the stream (2L - k + 1 per record
+// at soff): position i of a record carries the class of circular window i mod L, position 0 also F_REC.  Eight
+// positions = one 8-byte word per thread, zero behind n.
+__global__ __launch_bounds__(NT) void unroll_kernel(const u8 *cls, const u64 *win_off, const u64 *soff, u64 n_rec, u64 n, u8 *flag) {
+    const u64 p0 = ((u64)blockIdx.x * NT + threadIdx.x) * VT;
+    if (p0 >= n) return;
+    u64 r = upper_bound_u64(soff, n_rec + 1, p0) - 1;  // (records without positions share their offset with the next one)
+    u64 s0 = soff[r], s1 = soff[r + 1], w0 = win_off[r], len = win_off[r + 1] - w0;
+    u64 f8 = 0;
+#pragma unroll
+    for (int s = 0; s < VT; s++) {
+        const u64 p = p0 + s;
+        if (p >= n) break;
+        while (p >= s1) {  // (p < n = soff[n_rec]: ends at a record with positions)
+            r++;
+            s0 = s1; s1 = soff[r + 1]; w0 = win_off[r]; len = win_off[r + 1] - w0;
+        }
+        const u64 i = p - s0;
+        const u32 f = (u32)cls[w0 + (i >= len ? i - len : i)] | (i == 0 ? (u32)F_REC : 0u);
+        f8 |= (u64)f << (8 * s);
+    }
+    *reinterpret_cast<u64 *>(flag + p0) = f8;
+}
+
+// One run per thread.  The separator in front of run j is HARD when j is the first run, when more than max_gap_size
+// positions lie between the two runs, or when a break does (a multiple-mapped window, or the start of a record: the
+// break counts of the two runs differ).  A chain = a hard run and the soft ones behind it: cid[j] = hard runs up to and
+// including j, minus one; heads[c] = first run of chain c, heads[number of chains] = nruns.
+struct ChainArgs {
+    const u32 *start, *end, *brk;
+    u64 nruns;
+    u64 max_gap_size;
+    u32 *cid;    // [nruns]
+    u32 *heads;  // [nruns + 1]
+    u64 *status;
+    u32 *ticket;
+    u64 *result;  // [0] number of chains, [1] flags
+    u64 ntiles;
+};
+
+template <bool TICKET>
+__global__ __launch_bounds__(NT) void chain_kernel(ChainArgs p) {
+    __shared__ u32 s_scan[NT / 64 + 1];
+    __shared__ u64 s_misc[2];
+    const int tid = (int)threadIdx.x, lane = lane_id();
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
+    const u64 j = tile * (u64)NT + (u64)tid;
+    bool hard = false;
+    if (j < p.nruns)
+        hard = j == 0 || p.brk[j] != p.brk[j - 1] || (u64)(p.start[j] - p.end[j - 1] - 1u) > p.max_gap_size;
+    u32 tot;
+    const u32 excl = block_excl_scan_u32<NT>(hard ? 1u : 0u, s_scan, &tot);
+    const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tot, &p.result[1], MAP_FLAG_TIMEOUT, &s_misc[1], tid, lane);
+    if (j < p.nruns) {
+        const u64 c = base + excl + (hard ? 1u : 0u) - 1;  // (run 0 is hard: never negative)
+        p.cid[j] = (u32)c;
+        if (hard) p.heads[c] = (u32)j;
+    }
+    if (tid == 0 && tile == p.ntiles - 1) {
+        p.result[0] = base + tot;
+        p.heads[base + tot] = (u32)p.nruns;
+    }
+}
+
+struct EmitGappedArgs {
+    const u32 *start, *end, *cid, *heads;
+    u64 nruns;
+    const u64 *soff;     // [n_rec + 1] first stream position of every record
+    const u64 *rec_off;  // [n_rec + 1]
+    u64 n_rec;
+    int k, circular;
+    u64 min_len;
+    u64 max_gap_num;
+    u32 *out_rec;
+    u64 *out_start, *out_end;
+    u64 out_cap;
+    u64 *status;
+    u32 *ticket;
+    u64 *result;
+    u64 ntiles;
+};
+
+// One run per thread.  Inside a chain the state machine of map.go:362-489 closes a region at the (X + 1)-th small gap,
+// X = max_gap_num, and opens the next one at the run behind that gap: the regions are the groups of X + 1 consecutive
+// runs counted from the chain's head, the last group cut at the chain's end.  A run that heads a group emits it.
+template <bool TICKET>
+__global__ __launch_bounds__(NT) void emit_gapped_kernel(EmitGappedArgs p) {
+    __shared__ u32 s_scan[NT / 64 + 1];
+    __shared__ u64 s_misc[2];
+    const int tid = (int)threadIdx.x, lane = lane_id();
+    const u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
+    const u64 j = tile * (u64)NT + (u64)tid;
+    u64 r = 0, s = 0, e = 0;
+    bool keep = false;
+    if (j < p.nruns) {
+        const u32 c = p.cid[j];
+        if ((j - (u64)p.heads[c]) % (p.max_gap_num + 1) == 0) {
+            const u64 chain_last = (u64)p.heads[c + 1] - 1;
+            const u64 last = j + p.max_gap_num < chain_last ? j + p.max_gap_num : chain_last;
+            const u64 first_pos = p.start[j];
+            const u64 span = (u64)p.end[last] - first_pos + (u64)p.k;  // lastmatch - start + k
+            r = upper_bound_u64(p.soff, p.n_rec + 1, first_pos) - 1;
+            s = first_pos - p.soff[r];
+            e = s + span;
+            keep = span >= p.min_len;
+            if (p.circular) {
+                const u64 len = p.rec_off[r + 1] - p.rec_off[r];
+                if (s >= len) keep = false;    // a start in the second copy (map.go:407/423)
+                if (span > len) e = s + len;   // longer than the record itself (map.go:381)
+            }
+        }
+    }
+    u32 tot;
+    const u32 excl = block_excl_scan_u32<NT>(keep ? 1u : 0u, s_scan, &tot);
+    const u64 base = lb_tile_base<TICKET>(p.status, tile, (u64)tot, &p.result[1], MAP_FLAG_TIMEOUT, &s_misc[1], tid, lane);
+    const u64 pos = base + excl;
+    if (keep && pos < p.out_cap) {
+        p.out_rec[pos] = (u32)r;
+        p.out_start[pos] = s;
+        p.out_end[pos] = e;
     }
     if (tid == 0 && tile == p.ntiles - 1) p.result[0] = base + tot;
 }
@@ -420,16 +576,200 @@ extern "C" int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *re
     return ukm_finish(&s, rc);
 }
 
-extern "C" int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
-                       uint64_t n_genome, int k, int hashed, const uint64_t *set_keys, uint64_t n_set, int allow_multi,
-                       uint64_t min_len, uint32_t *out_rec, uint64_t *out_start, uint64_t *out_end, uint64_t out_cap,
-                       uint64_t *n_out) {
-    const char *name = "ukm_map";
+// ---- ukm_map / ukm_map_gapped -------------------------------------------------------------------------------------------
+namespace {
+
+// one look-back launch over `ntiles` tiles: control block, the watchdog ladder, result word [0]
+template <typename Args, typename Launch>
+int lb_pass(ukm_ctx *c, const char *name, const char *kernel_name, Args &p, u64 ntiles, Launch launch, u64 *count) {
+    p.ntiles = ntiles;
+    LbCtl blk;
+    UKM_TRY(ukm_lb_ctl_alloc(c, ntiles, 0, &blk));
+    p.status = blk.status; p.ticket = blk.ticket; p.result = blk.result;
+    u64 res[2] = {0, 0};
+    const LbLaunch how = {name, kernel_name, MAP_FLAG_TIMEOUT, false, false, false};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+        launch(ticket);
+        return UKM_OK;
+    }, res));
+    *count = res[0];
+    return UKM_OK;
+}
+
+struct MapOpts {
+    int circular = 0;
+    u64 max_gap_size = 0, max_gap_num = 0;
+};
+
+// Everything behind the argument checks.  Without gaps and on linear records a region is a run (runs_kernel, emit_kernel);
+// otherwise the runs of the stream are chained and grouped (runs_kernel with break counts, chain_kernel, emit_gapped_kernel).
+int map_regions(ukm_ctx *ctx, const char *name, const u8 *bases, const u64 *rec_off, u64 n_rec, const u64 *genome_off, u64 n_genome,
+                int k, int hashed, const u64 *set_keys, u64 n_set, int allow_multi, u64 min_len, const MapOpts &o, u32 *orec,
+                u64 *ostart, u64 *oend, u64 out_cap, u64 *n_out) {
+    // genome_off: checked on the host (it is small), used on the device
+    const u64 *goff = nullptr;
+    UKM_TRY(ukm_in_t(ctx, genome_off, n_genome + 1, &goff));
+    {
+        std::vector<u64> gh(n_genome + 1);
+        if (ukm_is_device_ptr(genome_off)) {
+            UKM_HIP(hipMemcpyAsync(gh.data(), goff, gh.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+            UKM_HIP(hipStreamSynchronize(ctx->stream));
+        } else {
+            memcpy(gh.data(), genome_off, gh.size() * sizeof(u64));
+        }
+        bool ok = gh[0] == 0 && gh[n_genome] == n_rec;
+        for (u64 g = 0; ok && g < n_genome; g++) ok = gh[g] <= gh[g + 1];
+        if (!ok) UKM_FAIL(UKM_ERR_INVALID, "%s: genome_off must rise from 0 to n_rec", name);
+    }
+    const u64 *set = nullptr;
+    UKM_TRY(ukm_in_t(ctx, set_keys, n_set, &set));
+    bool sorted = true, strict = true;
+    UKM_TRY(ukm_dev_check_sorted(ctx, set, n_set, &sorted, &strict));
+    if (!sorted) UKM_FAIL(UKM_ERR_UNSORTED, "%s: the code set is not sorted", name);
+    Windows W;  // (circular: the L circular windows of every record, the ones map.go:222-226 counts multiplicity among)
+    UKM_TRY(make_windows(ctx, name, bases, rec_off, n_rec, k, o.circular, hashed, &W));
+    if (W.n == 0 || n_set == 0) return UKM_OK;
+    const bool plain = !o.circular && o.max_gap_size == 0;
+    if (!plain && !o.circular && W.n >= (1ull << 31))
+        UKM_FAIL(UKM_ERR_INVALID, "%s: %llu stream positions in one call; the limit is 2^31 - 1 (run and break counts share one "
+                 "look-back word): split the records over several calls", name, (unsigned long long)W.n);
+    const int key_bits = hashed ? 64 : 2 * k;
+    Dir d;
+    UKM_TRY(build_dir(ctx, set, n_set, key_bits, dir_slack(ctx), &d));
+    u8 *flag = nullptr;
+    UKM_TRY(ws_alloc_t(ctx, flag_bytes(W.n), &flag));
+    Genomes G = {nullptr, n_genome};
+    if (!allow_multi && n_genome > 1) {
+        u64 *gwin = nullptr;
+        UKM_TRY(ws_alloc_t(ctx, n_genome + 1, &gwin));
+        hipLaunchKernelGGL(genome_windows_kernel, dim3(blocks_for(n_genome + 1)), dim3(NT), 0, ctx->stream, goff, W.win_off, n_genome, gwin);
+        G.gwin = gwin;
+    }
+    if (sorted_route(ctx, n_set, MAP_SORTED_MIN_KEYS)) {
+        // every (code, window) pair sorted, the set looked up in sorted order, the flags scattered back
+        u32 *wi = nullptr;
+        UKM_TRY(sort_windows(ctx, W.w, W.n, key_bits, &wi));
+        UKM_HIP(hipMemsetAsync(flag, 0, flag_bytes(W.n), ctx->stream));
+        (void)hipEventRecord(ctx->ev_k0, ctx->stream);
+        hipLaunchKernelGGL(sorted_classify_kernel, dim3(blocks_for(W.n)), dim3(NT), 0, ctx->stream, W.w, wi, W.n, d, G, allow_multi, flag);
+        (void)hipEventRecord(ctx->ev_k1, ctx->stream);
+        ctx->evk_valid = true;
+        UKM_HIP(hipGetLastError());
+    } else if (allow_multi) {
+        u64 nh = 0;
+        UKM_TRY(run_join(ctx, W.w, nullptr, W.n, d, flag, nullptr, false, nullptr, nullptr, 0, &nh));
+    } else {
+        // the hits, sorted by code: a multiple-mapped code's occurrences are neighbours
+        u64 *hk = nullptr;
+        u32 *hv = nullptr;
+        UKM_TRY(ws_alloc_t(ctx, W.n, &hk));
+        UKM_TRY(ws_alloc_t(ctx, W.n, &hv));
+        u64 nh = 0;
+        UKM_TRY(run_join(ctx, W.w, nullptr, W.n, d, flag, nullptr, true, hk, hv, W.n, &nh));
+        if (nh > 1) {
+            UKM_TRY(ukm_dev_sort(ctx, hk, hv, nh, key_bits));
+            hipLaunchKernelGGL(classify_kernel, dim3(blocks_for(nh)), dim3(NT), 0, ctx->stream, hk, hv, nh, G, flag);
+            UKM_HIP(hipGetLastError());
+        }
+    }
+    // the stream the runs are found on: the windows themselves, or every circular record's windows written out twice
+    const u64 *soff = W.win_off;
+    u64 ns = W.n;
+    if (o.circular) {
+        u64 *cnt = nullptr, *so = nullptr, *total_dev = nullptr;
+        UKM_TRY(ws_alloc_t(ctx, n_rec + 1, &cnt));
+        UKM_TRY(ws_alloc_t(ctx, n_rec + 1, &so));
+        UKM_TRY(ws_alloc_t(ctx, 1, &total_dev));
+        hipLaunchKernelGGL(stream_count_kernel, dim3(blocks_for(n_rec + 1)), dim3(NT), 0, ctx->stream, W.rec_off, n_rec, k, cnt);
+        UKM_TRY(ukm_dev_exclusive_scan_u64(ctx, cnt, so, n_rec + 1, total_dev));
+        UKM_TRY(ukm_read_u64(ctx, total_dev, &ns));
+        if (ns >= (1ull << 31))
+            UKM_FAIL(UKM_ERR_INVALID, "%s: %llu stream positions in one call (2L - k + 1 per circular record); the limit is 2^31 - 1 "
+                     "(run and break counts share one look-back word): split the records over several calls", name, (unsigned long long)ns);
+        u8 *sflag = nullptr;
+        UKM_TRY(ws_alloc_t(ctx, flag_bytes(ns), &sflag));
+        hipLaunchKernelGGL(unroll_kernel, dim3((unsigned)((ns + TILE - 1) / TILE)), dim3(NT), 0, ctx->stream, flag, W.win_off, so, n_rec, ns, sflag);
+        UKM_HIP(hipGetLastError());
+        flag = sflag;
+        soff = so;
+    } else {
+        hipLaunchKernelGGL(mark_rec_kernel, dim3(blocks_for(n_rec)), dim3(NT), 0, ctx->stream, W.win_off, n_rec, flag);
+        UKM_HIP(hipGetLastError());
+    }
+    // run starts and ends (records of one good window each: as many runs as positions)
+    const u64 rcap = ns;
+    u32 *rs = nullptr, *re = nullptr, *rb = nullptr;
+    UKM_TRY(ws_alloc_t(ctx, rcap, &rs));
+    UKM_TRY(ws_alloc_t(ctx, rcap, &re));
+    if (!plain) UKM_TRY(ws_alloc_t(ctx, rcap, &rb));
+    u64 nruns = 0;
+    {
+        RunArgs p;
+        memset(&p, 0, sizeof(p));
+        p.flag = flag; p.n = ns; p.start = rs; p.end = re; p.brk = rb; p.cap = rcap;
+        const unsigned nt = (unsigned)((ns + TILE - 1) / TILE);
+        UKM_TRY(lb_pass(ctx, name, "run kernel", p, nt, [&](bool ticket) {
+            if (plain) {
+                if (ticket) hipLaunchKernelGGL((runs_kernel<true, false>), dim3(nt), dim3(NT), 0, ctx->stream, p);
+                else hipLaunchKernelGGL((runs_kernel<false, false>), dim3(nt), dim3(NT), 0, ctx->stream, p);
+            } else {
+                if (ticket) hipLaunchKernelGGL((runs_kernel<true, true>), dim3(nt), dim3(NT), 0, ctx->stream, p);
+                else hipLaunchKernelGGL((runs_kernel<false, true>), dim3(nt), dim3(NT), 0, ctx->stream, p);
+            }
+        }, &nruns));
+    }
+    if (nruns == 0) return UKM_OK;
+    const unsigned rt = (unsigned)((nruns + NT - 1) / NT);
+    if (plain) {
+        EmitArgs p;
+        memset(&p, 0, sizeof(p));
+        p.start = rs; p.end = re; p.nruns = nruns; p.win_off = W.win_off; p.n_rec = n_rec; p.k = k; p.min_len = min_len;
+        p.out_rec = orec; p.out_start = ostart; p.out_end = oend; p.out_cap = out_cap;
+        UKM_TRY(lb_pass(ctx, name, "region kernel", p, rt, [&](bool ticket) {
+            if (ticket) hipLaunchKernelGGL((emit_kernel<true>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+            else hipLaunchKernelGGL((emit_kernel<false>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+        }, n_out));
+    } else {
+        u32 *cid = nullptr, *heads = nullptr;
+        UKM_TRY(ws_alloc_t(ctx, nruns, &cid));
+        UKM_TRY(ws_alloc_t(ctx, nruns + 1, &heads));
+        u64 nchains = 0;
+        {
+            ChainArgs p;
+            memset(&p, 0, sizeof(p));
+            p.start = rs; p.end = re; p.brk = rb; p.nruns = nruns; p.max_gap_size = o.max_gap_size; p.cid = cid; p.heads = heads;
+            UKM_TRY(lb_pass(ctx, name, "chain kernel", p, rt, [&](bool ticket) {
+                if (ticket) hipLaunchKernelGGL((chain_kernel<true>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+                else hipLaunchKernelGGL((chain_kernel<false>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+            }, &nchains));
+        }
+        EmitGappedArgs p;
+        memset(&p, 0, sizeof(p));
+        p.start = rs; p.end = re; p.cid = cid; p.heads = heads; p.nruns = nruns; p.soff = soff; p.rec_off = W.rec_off; p.n_rec = n_rec;
+        p.k = k; p.circular = o.circular; p.min_len = min_len; p.max_gap_num = o.max_gap_size ? o.max_gap_num : 0;
+        p.out_rec = orec; p.out_start = ostart; p.out_end = oend; p.out_cap = out_cap;
+        UKM_TRY(lb_pass(ctx, name, "gapped region kernel", p, rt, [&](bool ticket) {
+            if (ticket) hipLaunchKernelGGL((emit_gapped_kernel<true>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+            else hipLaunchKernelGGL((emit_gapped_kernel<false>), dim3(rt), dim3(NT), 0, ctx->stream, p);
+        }, n_out));
+    }
+    if (*n_out > out_cap)
+        UKM_FAIL(UKM_ERR_CAPACITY, "%s: output needs %llu regions, capacity is %llu", name, (unsigned long long)*n_out, (unsigned long long)out_cap);
+    return UKM_OK;
+}
+
+int map_entry(const char *name, ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
+              uint64_t n_genome, int k, int hashed, const uint64_t *set_keys, uint64_t n_set, int allow_multi, uint64_t min_len,
+              const MapOpts &o, uint32_t *out_rec, uint64_t *out_start, uint64_t *out_end, uint64_t out_cap, uint64_t *n_out) {
     UKM_TRY(check_args(name, ctx, n_out, bases, rec_off, n_rec, k, hashed));
     if ((n_set && !set_keys) || (out_cap && (!out_rec || !out_start || !out_end)) || (n_rec && !genome_off))
         UKM_FAIL(UKM_ERR_INVALID, "%s: NULL argument", name);
     if (min_len < 1) UKM_FAIL(UKM_ERR_INVALID, "%s: min_len must be at least 1", name);
     if (n_set >= (1ull << 32)) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu codes in the set; the limit is 2^32 - 1", name, (unsigned long long)n_set);
+    if (o.max_gap_size > 0x7FFFFFFFull || o.max_gap_num > 0x7FFFFFFFull)
+        UKM_FAIL(UKM_ERR_INVALID, "%s: max_gap_size and max_gap_num must be below 2^31", name);
+    if (o.max_gap_size > 0 && o.max_gap_num == 0)
+        UKM_FAIL(UKM_ERR_INVALID, "%s: max_gap_num must be above 0 when max_gap_size is (map.go:112)", name);
     *n_out = 0;
     if (n_rec == 0) return UKM_OK;
     if (n_genome == 0) UKM_FAIL(UKM_ERR_INVALID, "%s: records need at least one genome", name);
@@ -441,123 +781,35 @@ extern "C" int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_o
         UKM_TRY(ukm_out_t(ctx, out_rec, out_cap, &orec));
         UKM_TRY(ukm_out_t(ctx, out_start, out_cap, &ostart));
         UKM_TRY(ukm_out_t(ctx, out_end, out_cap, &oend));
-        auto sizes = [&](u64 n) {
-            ukm_out_resize(ctx, out_rec, n * sizeof(u32));
-            ukm_out_resize(ctx, out_start, n * sizeof(u64));
-            ukm_out_resize(ctx, out_end, n * sizeof(u64));
-        };
-        const int r = [&]() -> int {
-        // genome_off: checked on the host (it is small), used on the device
-        const u64 *goff = nullptr;
-        UKM_TRY(ukm_in_t(ctx, genome_off, n_genome + 1, &goff));
-        {
-            std::vector<u64> gh(n_genome + 1);
-            if (ukm_is_device_ptr(genome_off)) {
-                UKM_HIP(hipMemcpyAsync(gh.data(), goff, gh.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-                UKM_HIP(hipStreamSynchronize(ctx->stream));
-            } else {
-                memcpy(gh.data(), genome_off, gh.size() * sizeof(u64));
-            }
-            bool ok = gh[0] == 0 && gh[n_genome] == n_rec;
-            for (u64 g = 0; ok && g < n_genome; g++) ok = gh[g] <= gh[g + 1];
-            if (!ok) UKM_FAIL(UKM_ERR_INVALID, "%s: genome_off must rise from 0 to n_rec", name);
-        }
-        const u64 *set = nullptr;
-        UKM_TRY(ukm_in_t(ctx, set_keys, n_set, &set));
-        bool sorted = true, strict = true;
-        UKM_TRY(ukm_dev_check_sorted(ctx, set, n_set, &sorted, &strict));
-        if (!sorted) UKM_FAIL(UKM_ERR_UNSORTED, "%s: the code set is not sorted", name);
-        Windows W;
-        UKM_TRY(make_windows(ctx, name, bases, rec_off, n_rec, k, 0, hashed, &W));
-        if (W.n == 0 || n_set == 0) return UKM_OK;
-        const int key_bits = hashed ? 64 : 2 * k;
-        Dir d;
-        UKM_TRY(build_dir(ctx, set, n_set, key_bits, dir_slack(ctx), &d));
-        u8 *flag = nullptr;
-        UKM_TRY(ws_alloc_t(ctx, flag_bytes(W.n), &flag));
-        Genomes G = {nullptr, n_genome};
-        if (!allow_multi && n_genome > 1) {
-            u64 *gwin = nullptr;
-            UKM_TRY(ws_alloc_t(ctx, n_genome + 1, &gwin));
-            hipLaunchKernelGGL(genome_windows_kernel, dim3(blocks_for(n_genome + 1)), dim3(NT), 0, ctx->stream, goff, W.win_off, n_genome, gwin);
-            G.gwin = gwin;
-        }
-        if (sorted_route(ctx, n_set, MAP_SORTED_MIN_KEYS)) {
-            // every (code, window) pair sorted, the set looked up in sorted order, the flags scattered back
-            u32 *wi = nullptr;
-            UKM_TRY(sort_windows(ctx, W.w, W.n, key_bits, &wi));
-            UKM_HIP(hipMemsetAsync(flag, 0, flag_bytes(W.n), ctx->stream));
-            (void)hipEventRecord(ctx->ev_k0, ctx->stream);
-            hipLaunchKernelGGL(sorted_classify_kernel, dim3(blocks_for(W.n)), dim3(NT), 0, ctx->stream, W.w, wi, W.n, d, G, allow_multi, flag);
-            (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-            ctx->evk_valid = true;
-            UKM_HIP(hipGetLastError());
-        } else if (allow_multi) {
-            u64 nh = 0;
-            UKM_TRY(run_join(ctx, W.w, nullptr, W.n, d, flag, nullptr, false, nullptr, nullptr, 0, &nh));
-        } else {
-            // the hits, sorted by code: a multiple-mapped code's occurrences are neighbours
-            u64 *hk = nullptr;
-            u32 *hv = nullptr;
-            UKM_TRY(ws_alloc_t(ctx, W.n, &hk));
-            UKM_TRY(ws_alloc_t(ctx, W.n, &hv));
-            u64 nh = 0;
-            UKM_TRY(run_join(ctx, W.w, nullptr, W.n, d, flag, nullptr, true, hk, hv, W.n, &nh));
-            if (nh > 1) {
-                UKM_TRY(ukm_dev_sort(ctx, hk, hv, nh, key_bits));
-                hipLaunchKernelGGL(classify_kernel, dim3(blocks_for(nh)), dim3(NT), 0, ctx->stream, hk, hv, nh, G, flag);
-                UKM_HIP(hipGetLastError());
-            }
-        }
-        hipLaunchKernelGGL(mark_rec_kernel, dim3(blocks_for(n_rec)), dim3(NT), 0, ctx->stream, W.win_off, n_rec, flag);
-        UKM_HIP(hipGetLastError());
-        // run starts and ends
-        u32 *rs = nullptr, *re = nullptr;
-        UKM_TRY(ws_alloc_t(ctx, W.n, &rs));
-        UKM_TRY(ws_alloc_t(ctx, W.n, &re));
-        u64 nruns = 0;
-        {
-            RunArgs p;
-            memset(&p, 0, sizeof(p));
-            p.flag = flag; p.n = W.n; p.start = rs; p.end = re; p.cap = W.n;
-            p.ntiles = (W.n + TILE - 1) / TILE;
-            LbCtl blk;
-            UKM_TRY(ukm_lb_ctl_alloc(ctx, p.ntiles, 0, &blk));
-            p.status = blk.status; p.ticket = blk.ticket; p.result = blk.result;
-            u64 res[2] = {0, 0};
-            const LbLaunch how = {"ukm_map", "run kernel", MAP_FLAG_TIMEOUT, false, false, false};
-            UKM_TRY(ukm_lb_launch(ctx, blk, how, [&](bool ticket) {
-                if (ticket) hipLaunchKernelGGL((runs_kernel<true>), dim3((unsigned)p.ntiles), dim3(NT), 0, ctx->stream, p);
-                else hipLaunchKernelGGL((runs_kernel<false>), dim3((unsigned)p.ntiles), dim3(NT), 0, ctx->stream, p);
-                return UKM_OK;
-            }, res));
-            nruns = res[0];
-        }
-        if (nruns == 0) return UKM_OK;
-        {
-            EmitArgs p;
-            memset(&p, 0, sizeof(p));
-            p.start = rs; p.end = re; p.nruns = nruns; p.win_off = W.win_off; p.n_rec = n_rec; p.k = k; p.min_len = min_len;
-            p.out_rec = orec; p.out_start = ostart; p.out_end = oend; p.out_cap = out_cap;
-            p.ntiles = (nruns + NT - 1) / NT;
-            LbCtl blk;
-            UKM_TRY(ukm_lb_ctl_alloc(ctx, p.ntiles, 0, &blk));
-            p.status = blk.status; p.ticket = blk.ticket; p.result = blk.result;
-            u64 res[2] = {0, 0};
-            const LbLaunch how = {"ukm_map", "region kernel", MAP_FLAG_TIMEOUT, false, false, false};
-            UKM_TRY(ukm_lb_launch(ctx, blk, how, [&](bool ticket) {
-                if (ticket) hipLaunchKernelGGL((emit_kernel<true>), dim3((unsigned)p.ntiles), dim3(NT), 0, ctx->stream, p);
-                else hipLaunchKernelGGL((emit_kernel<false>), dim3((unsigned)p.ntiles), dim3(NT), 0, ctx->stream, p);
-                return UKM_OK;
-            }, res));
-            *n_out = res[0];
-        }
-        if (*n_out > out_cap)
-            UKM_FAIL(UKM_ERR_CAPACITY, "%s: output needs %llu regions, capacity is %llu", name, (unsigned long long)*n_out, (unsigned long long)out_cap);
-        return UKM_OK;
-        }();
-        sizes(r == UKM_OK ? *n_out : 0);
+        const int r = map_regions(ctx, name, bases, rec_off, n_rec, genome_off, n_genome, k, hashed, set_keys, n_set, allow_multi, min_len, o,
+                                  orec, ostart, oend, out_cap, n_out);
+        const u64 n = r == UKM_OK ? *n_out : 0;  // (the copy-back of host outputs: what was written, nothing after an error)
+        ukm_out_resize(ctx, out_rec, n * sizeof(u32));
+        ukm_out_resize(ctx, out_start, n * sizeof(u64));
+        ukm_out_resize(ctx, out_end, n * sizeof(u64));
         return r;
     }();
     return ukm_finish(&s, rc);
+}
+
+}  // namespace
+
+extern "C" int ukm_map(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
+                       uint64_t n_genome, int k, int hashed, const uint64_t *set_keys, uint64_t n_set, int allow_multi,
+                       uint64_t min_len, uint32_t *out_rec, uint64_t *out_start, uint64_t *out_end, uint64_t out_cap,
+                       uint64_t *n_out) {
+    return map_entry("ukm_map", ctx, bases, rec_off, n_rec, genome_off, n_genome, k, hashed, set_keys, n_set, allow_multi, min_len, MapOpts(),
+                     out_rec, out_start, out_end, out_cap, n_out);
+}
+
+extern "C" int ukm_map_gapped(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_off,
+                              uint64_t n_genome, int k, int hashed, int circular, const uint64_t *set_keys, uint64_t n_set,
+                              int allow_multi, uint64_t min_len, uint64_t max_gap_size, uint64_t max_gap_num, uint32_t *out_rec,
+                              uint64_t *out_start, uint64_t *out_end, uint64_t out_cap, uint64_t *n_out) {
+    MapOpts o;
+    o.circular = circular != 0;
+    o.max_gap_size = max_gap_size;
+    o.max_gap_num = max_gap_num;
+    return map_entry("ukm_map_gapped", ctx, bases, rec_off, n_rec, genome_off, n_genome, k, hashed, set_keys, n_set, allow_multi, min_len, o,
+                     out_rec, out_start, out_end, out_cap, n_out);
 }

@@ -37,7 +37,7 @@ SYMBOLS = [
     "ukm_shard_splitters", "ukm_shard_splitters_plan", "ukm_shard_counts_tax", "ukm_shard_counts_plan", "ukm_count",
     "ukm_ctx_set_option", "ukm_ctx_unset_option", "ukm_ctx_get_option", "ukm_ctx_get_stat",
     "ukm_setop2_ft", "ukm_union_ft", "ukm_inter_ft", "ukm_diff_ft", "ukm_common_ft", "ukm_merge_k_ft",
-    "ukm_locate", "ukm_map", "ukm_grep", "ukm_filter", "ukm_sample",
+    "ukm_locate", "ukm_map", "ukm_map_gapped", "ukm_grep", "ukm_filter", "ukm_sample",
     "ukm_taxonomy_set_ranks", "ukm_rank_filter_plan", "ukm_rank_pass", "ukm_rfilter", "ukm_tsplit",
 ]
 
@@ -162,6 +162,7 @@ def load():
     L.ukm_count.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, u64, i32, vp, u64, pu64]
     L.ukm_locate.argtypes = [vp, vp, vp, u64, i32, i32, i32, vp, u64, vp, vp, vp, u64, pu64]
     L.ukm_map.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, vp, u64, i32, u64, vp, vp, vp, u64, pu64]
+    L.ukm_map_gapped.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, i32, vp, u64, i32, u64, u64, u64, vp, vp, vp, u64, pu64]
     L.ukm_grep.argtypes = [vp, vp, vp, u32, u64, i32, vp, vp, u64, u32, vp, vp, u64, pu64]
     L.ukm_filter.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, i32, u32, vp, vp, u64, pu64]
     L.ukm_sample.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, u64, pu64]
@@ -534,6 +535,23 @@ class Context:
         ps, ns, k4 = _ptr(set_keys, np.uint64)
         return self._coords(lambda o, cap, n: self.L.ukm_map(self.h, pb, poff, noff - 1, pg, ng - 1, int(k), int(hashed), ps, ns,
                                                              int(allow_multi), int(min_len), o[0], o[1], o[2], cap, C.byref(n)),
+                            bases, (np.uint32, np.uint64, np.uint64), out_cap, outs)
+
+    def map_gapped(self, bases, rec_off, genome_off, k, set_keys, hashed=False, circular=False, allow_multi=False, min_len=200,
+                   max_gap_size=0, max_gap_num=0, out_cap=None, outs=None):
+        """`unikmer map` / `uniqs` with -x max_gap_size, -X max_gap_num and --circular (map.go:298-490; the definition and the
+        two deviations from the reference: include/unikmer_hip.h, ukm_map_gapped).  Returns (rec, start, end) per region, in
+        record then start order; on circular records end may exceed the record's length.  max_gap_size = 0 on linear
+        records is `map`."""
+        pb, _, k1 = _ptr(bases, np.uint8)
+        poff, noff, k2 = _ptr(rec_off, np.uint64)
+        if genome_off is None:
+            genome_off = np.arange(noff, dtype=np.uint64)
+        pg, ng, k3 = _ptr(genome_off, np.uint64)
+        ps, ns, k4 = _ptr(set_keys, np.uint64)
+        return self._coords(lambda o, cap, n: self.L.ukm_map_gapped(self.h, pb, poff, noff - 1, pg, ng - 1, int(k), int(hashed), int(circular),
+                                                                    ps, ns, int(allow_multi), int(min_len), int(max_gap_size),
+                                                                    int(max_gap_num), o[0], o[1], o[2], cap, C.byref(n)),
                             bases, (np.uint32, np.uint64, np.uint64), out_cap, outs)
 
     # ---- record selection (grep / filter / sample): kept records in input order, taxids copied ----
