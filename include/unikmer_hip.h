@@ -174,7 +174,11 @@ int ukm_last_route(ukm_ctx *ctx);
  *      "setop_offs_hits" = of those hits, calls on plain codes (no taxids) whose pass also took the output offsets of its
  *      tiles from the match counts a call before it left with the table, and so ran without the look-back,
  *      "setop_offs_stale" = such calls whose tiles counted otherwise (contents rewritten in place under an unchanged
- *      partition): the pass ran again with the look-back (after two in a row the context stops trying).  See ukm_setop2. */
+ *      partition): the pass ran again with the look-back (after two in a row the context stops trying).  See ukm_setop2.
+ *      "lb_watchdogs" = times a look-back watchdog fired in this context (a tile's predecessor did not publish: the
+ *      launch was repeated with ticketed tile ids, or a chained inter / diff fold fell back to the synchronous fold),
+ *      "ticket_latched" = 1 once that has happened: every later look-back kernel of the context takes its tile ids from
+ *      tickets, for the context's lifetime (0 otherwise; option "force_ticket" does not show here). */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);

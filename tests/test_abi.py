@@ -26,6 +26,25 @@ def test_header_symbols_exported(lib):
         assert hasattr(L, name), name
 
 
+def _exported_ukm(path):
+    """the ukm_* symbols a shared library defines and exports, read without loading it"""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ukm_")}
+
+
+def test_seam_library_exports_the_same_symbols(lib):
+    """build() also leaves the look-back test library (tests/test_gpu_lb_retry.py): the same sources, six of them compiled
+    with UKM_LB_TEST_TIMEOUT -- the same C ABI, symbol for symbol"""
+    from unikmer_amd import build
+    assert os.path.exists(build.SO_LBTEST)
+    product, seam = _exported_ukm(build.SO), _exported_ukm(build.SO_LBTEST)
+    assert set(lib.SYMBOLS) <= product, set(lib.SYMBOLS) - product
+    assert seam == product, seam ^ product
+
+
 def test_pure_host_entry_points(lib):
     L = lib.load()
     assert L.ukm_version() >= 1

@@ -1,4 +1,5 @@
-"""Builds libunikmer_hip.so (gfx950) in-tree with hipcc.  `python -m unikmer_amd.build`."""
+"""Builds libunikmer_hip.so (gfx950) in-tree with hipcc, and the test library libunikmer_hip_lbtest.so beside it.
+`python -m unikmer_amd.build`."""
 import os
 import subprocess
 import sys
@@ -9,6 +10,12 @@ SO = os.path.join(HERE, "libunikmer_hip.so")
 SOURCES = ["ukm_ctx.hip", "ukm_setops.hip", "ukm_scan.hip", "ukm_sort.hip", "ukm_encode.hip",
            "ukm_tax.hip", "ukm_nway.hip", "ukm_kway.hip", "ukm_comm.hip", "ukm_fold.hip", "ukm_probe.hip", "ukm_probe_union.hip", "ukm_probe_ranked.hip", "ukm_place.hip", "ukm_pfold.hip", "ukm_srmerge.hip", "ukm_route.hip", "ukm_map.hip", "ukm_select.hip", "ukm_tsplit.hip"]
 HEADERS = ["ukm_internal.h", "ukm_device.h", "ukm_kway.h", "ukm_fold.h", "ukm_probe.h", "ukm_pfold.h", "ukm_srmerge.h", "ukm_route.h", "ukm_map.h", "ukm_dir.h", os.path.join("..", "..", "include", "unikmer_hip.h")]
+# The test library (tests/test_gpu_lb_retry.py): the sources that include the decoupled look-back, compiled once more with
+# the watchdog's injection seam of ukm_device.h (UKM_LB_TEST_TIMEOUT) into objects of their own, and linked with the product
+# objects of all other sources.  The product library never sees the macro.
+SO_LBTEST = os.path.join(HERE, "libunikmer_hip_lbtest.so")
+LBTEST_SOURCES = ["ukm_setops.hip", "ukm_scan.hip", "ukm_encode.hip", "ukm_select.hip", "ukm_tsplit.hip", "ukm_map.hip"]
+LBTEST_FLAG = "-DUKM_LB_TEST_TIMEOUT"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -29,18 +36,26 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []
+    objs_lbtest = []
     procs = []
-    for src in SOURCES:
+    jobs = [(src, src.replace(".hip", ".o"), []) for src in SOURCES]
+    jobs += [(src, src.replace(".hip", "_lbtest.o"), [LBTEST_FLAG]) for src in LBTEST_SOURCES]
+    for src, obj, extra in jobs:
         s = os.path.join(CSRC, src)
-        o = os.path.join(CSRC, src.replace(".hip", ".o"))
-        objs.append(o)
+        o = os.path.join(CSRC, obj)
+        if not extra:
+            objs.append(o)
+            if src not in LBTEST_SOURCES:
+                objs_lbtest.append(o)
+        else:
+            objs_lbtest.append(o)
         if force or _stale(o, [s] + hdrs):
-            cmd = [_hipcc()] + FLAGS + ["-c", s, "-o", o]
+            cmd = [_hipcc()] + FLAGS + extra + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd))
-            procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            procs.append((src, o, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     failed = False
-    for src, p in procs:
+    for src, o, p in procs:
         out, _ = p.communicate()
         text = out.decode(errors="replace")
         if p.returncode != 0:
@@ -53,7 +68,7 @@ def build(force=False, verbose=False):
             first = [ln for ln in text.splitlines() if "reserved registers" in ln or "occupancy target" in ln][:3]
             sys.stderr.write("register-budget check failed for %s:\n%s\n" % (src, "\n".join(first)))
             try:
-                os.remove(os.path.join(CSRC, src.replace(".hip", ".o")))
+                os.remove(o)
             except OSError:
                 pass
         elif verbose and out:
@@ -62,6 +77,11 @@ def build(force=False, verbose=False):
         raise RuntimeError("building libunikmer_hip.so failed")
     if force or procs or _stale(SO, objs):
         cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO] + objs + ["-ldl"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    if force or procs or _stale(SO_LBTEST, objs_lbtest):
+        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO_LBTEST] + objs_lbtest + ["-ldl"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -113,6 +113,8 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "setop_offs_hits") == 0) *value = c->stat_setop_offs_hits;
     else if (strcmp(key, "setop_offs_stale") == 0) *value = c->stat_setop_offs_stale;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
+    else if (strcmp(key, "lb_watchdogs") == 0) *value = c->stat_lb_watchdogs;
+    else if (strcmp(key, "ticket_latched") == 0) *value = c->ticket_latched ? 1 : 0;
     else if (strcmp(key, "workspace_bytes") == 0) {
         u64 t = 0;
         for (auto &b : c->blocks) t += b.cap;
@@ -462,6 +464,7 @@ void ukm_switch_to_tickets(ukm_ctx *c, const char *where) {
                         "switching this context to ticketed tile ids\n", where, c->device);
     c->ticket_latched = true;
     c->setop_force_ticket = true;
+    c->stat_lb_watchdogs++;
 }
 
 int ukm_read_u64(ukm_ctx *c, const u64 *dev, u64 *host, int n) {

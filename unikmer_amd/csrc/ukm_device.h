@@ -166,7 +166,15 @@ __device__ __forceinline__ u64 lb_resolve(u64 *status, u64 tile, u64 agg, int la
 #else
     const bool skip_poll = false;
 #endif
+#ifdef UKM_LB_TEST_TIMEOUT
+    // Test seam (the second library of build.py; never defined in the product build): a tile >= 1 whose id came from
+    // blockIdx gives up before its first poll, exactly as if LB_SPIN_LIMIT polls had passed -- excl stays 0, so its base
+    // is never above the true one.  Everything behind the loop is the real code.  It removes waiting and adds none.
+    dead = timed_out != nullptr;
+    while (!dead) {
+#else
     for (;;) {
+#endif
         // wait for the nearest not-yet-counted predecessor with a single-word poll
         int ok = 1;
         if (lane == 0 && !skip_poll) {

@@ -239,6 +239,7 @@ struct ukm_ctx {
     bool setop_force_ticket = false;  // = ticket_latched || option "force_ticket"
     unsigned long long stat_sort_fused_hist = 0;  // sorts of this context that took their first histogram from the producer of the keys (ukm_count)
     bool ticket_latched = false;      // the look-back watchdog fired on this device (ukm_switch_to_tickets): stays set
+    unsigned long long stat_lb_watchdogs = 0;  // times ukm_switch_to_tickets ran: a launch ladder's retry, or a chained fold's fallback
     // set once a sort found its keys crowded into few top-16-bit buckets (ukm_sort.hip): later sorts look at a sample first
     bool sort_skew_seen = false;
     // buckets of the last bucket-route sort that fell back from the counting step to the digit passes (device word, bumped by

@@ -462,8 +462,13 @@ int fold_chained(ukm_ctx *ctx, int op, const std::vector<Stream> &ss, u32 flags,
     std::vector<u64> h((size_t)links * 8);
     UKM_HIP(hipMemcpyAsync(h.data(), ctl, h.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     UKM_HIP(hipStreamSynchronize(ctx->stream));
+    // A link whose watchdog fired leaves a partly written running result, and the links behind it have read that: it
+    // looks unsorted or full of duplicates to them.  Their flags say nothing about the inputs; the synchronous fold answers.
     u64 fl = 0;
-    for (int l = 0; l < links; l++) fl |= h[(size_t)l * 8 + 1];
+    for (int l = 0; l < links; l++) {
+        fl |= h[(size_t)l * 8 + 1];
+        if (fl & UKM_SETOP_FLAG_TIMEOUT) break;
+    }
     res->unsorted = (fl & UKM_SETOP_FLAG_UNSORTED) != 0;
     res->fallback = (fl & (UKM_SETOP_FLAG_DUP | UKM_SETOP_FLAG_TIMEOUT)) != 0;
     if (fl & UKM_SETOP_FLAG_TIMEOUT) ukm_switch_to_tickets(ctx, "chained set-op fold");
