@@ -226,6 +226,20 @@ class Reader {
         }
     }
 
+    // bulk: everything behind the header, inflated, as it stands in the file (what ukm_unik_decode takes).  Not to be
+    // mixed with read() on one Reader.
+    void read_body(std::vector<uint8_t> &body) {
+        size_t chunk = 1u << 22;
+        for (;;) {
+            const size_t at = body.size();
+            body.resize(at + chunk);
+            const size_t got = in_.read(body.data() + at, chunk);
+            body.resize(at + got);
+            if (got < chunk) break;
+            if (chunk < (1u << 28)) chunk <<= 1;
+        }
+    }
+
   private:
     uint32_t read_taxid() {
         uint8_t b[4];
@@ -331,6 +345,12 @@ class Writer {
         push(b, m);
         prev_ = code;
         have_first_ = false;
+    }
+
+    // bulk: the header, then an encoded body (what ukm_unik_encode gives) as it is.  Not to be mixed with write_code().
+    void write_body(const uint8_t *body, size_t n) {
+        write_header();
+        out_.write(body, n);
     }
 
     void flush() {

@@ -16,6 +16,8 @@ SO_PATH = os.environ.get("UKM_LIB_PATH") or os.path.join(_HERE, "libunikmer_hip.
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_ILLEGAL_BASE = -1, -2, -3, -4
 ERR_UNSORTED, ERR_NO_TAXONOMY, ERR_CAPACITY, ERR_K, ERR_PEER = -5, -6, -7, -8, -9
+ERR_FORMAT = -10   # a .unik body ends inside a record
+UNIK_COMPACT, UNIK_SORTED, UNIK_INCLUDE_TAXID = 1, 4, 8   # header flag bits the .unik codec looks at (unik.hpp)
 PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 F_MIX_TAXID, F_CMP_TAXID = 2, 4
@@ -39,6 +41,7 @@ SYMBOLS = [
     "ukm_setop2_ft", "ukm_union_ft", "ukm_inter_ft", "ukm_diff_ft", "ukm_common_ft", "ukm_merge_k_ft",
     "ukm_locate", "ukm_map", "ukm_map_gapped", "ukm_grep", "ukm_filter", "ukm_sample",
     "ukm_taxonomy_set_ranks", "ukm_rank_filter_plan", "ukm_rank_pass", "ukm_rfilter", "ukm_tsplit",
+    "ukm_unik_decode", "ukm_unik_encode", "ukm_unik_encode_bound",
 ]
 
 
@@ -84,6 +87,10 @@ class IllegalBaseError(UkmError):
 
 class UnsortedError(UkmError):
     pass
+
+
+class FormatError(UkmError):
+    """a .unik body ends inside a record (UKM_ERR_FORMAT)"""
 
 
 class CapacityError(UkmError):
@@ -171,6 +178,10 @@ def load():
     L.ukm_rank_pass.argtypes = [vp, vp, vp, u64, vp]
     L.ukm_rfilter.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, pu64]
     L.ukm_tsplit.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, pu64]
+    L.ukm_unik_decode.argtypes = [vp, vp, u64, i32, u32, i32, vp, vp, u64, pu64]
+    L.ukm_unik_encode.argtypes = [vp, vp, vp, u64, i32, u32, i32, vp, u64, pu64]
+    L.ukm_unik_encode_bound.argtypes = [u64, i32, u32, i32]
+    L.ukm_unik_encode_bound.restype = u64
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -225,7 +236,7 @@ def _check(rc, needed=None):
     msg = load().ukm_last_error().decode(errors="replace")
     if rc == ERR_CAPACITY:
         raise CapacityError(rc, msg, None if needed is None else int(needed))
-    cls = {ERR_ILLEGAL_BASE: IllegalBaseError, ERR_UNSORTED: UnsortedError}.get(rc, UkmError)
+    cls = {ERR_ILLEGAL_BASE: IllegalBaseError, ERR_UNSORTED: UnsortedError, ERR_FORMAT: FormatError}.get(rc, UkmError)
     raise cls(rc, msg)
 
 
@@ -259,6 +270,11 @@ def _empty_like_kind(ref, n, dtype):
         import torch
         return torch.empty(max(n, 1), dtype=getattr(torch, _NP2TORCH[np.dtype(dtype)]), device=ref.device)
     return np.empty(max(n, 1), dtype=dtype)
+
+
+def unik_encode_bound(n, k, flags, taxid_bytes=0):
+    """bytes a .unik body of n records takes at most (exact for the unsorted layouts); pure host code"""
+    return int(load().ukm_unik_encode_bound(int(n), int(k), int(flags), int(taxid_bytes)))
 
 
 class Context:
@@ -630,6 +646,39 @@ class Context:
         # group_off holds one entry more than group_taxids: the capacity is what both arrays take
         _check(self.L.ukm_tsplit(self.h, pk, pt, n, po, cap if n else 0, pg, pf, min(gcap, max(fcap, 1) - 1), C.byref(g)), g.value)
         return out[:n], group_taxids[: g.value], group_off[: g.value + 1 if n else 0]
+
+    # ---- .unik bodies (the bytes behind a file's header, inflated; layout: host/unik.hpp) ----
+    def unik_decode(self, body, k, flags, taxid_bytes=0, with_taxids=True, out=None, out_taxids=None):
+        """the records of a body: (keys, taxids), taxids None when the records carry none or with_taxids is False (the
+        taxid bytes are skipped then).  Without `out` the number of records is asked for first (the size query)."""
+        pb, nb, k1 = _ptr(body, np.uint8)
+        tax = bool(flags & UNIK_INCLUDE_TAXID) and (with_taxids or out_taxids is not None)
+        n = C.c_uint64()
+        if out is None:
+            rc = self.L.ukm_unik_decode(self.h, pb, nb, int(k), int(flags), int(taxid_bytes), None, None, 0, C.byref(n))
+            if rc != ERR_CAPACITY:
+                _check(rc)
+            out = _empty_like_kind(body, n.value, np.uint64)
+        po, cap, _ = _ptr(out, np.uint64)
+        if tax and out_taxids is None:
+            out_taxids = _empty_like_kind(body, cap, np.uint32)
+        pot, ncap, _ = _ptr(out_taxids if tax else None, np.uint32)
+        if tax:
+            cap = min(cap, ncap)
+        _check(self.L.ukm_unik_decode(self.h, pb, nb, int(k), int(flags), int(taxid_bytes), po, pot, cap if nb else 0, C.byref(n)), n.value)
+        return out[: n.value], (out_taxids[: n.value] if tax else None)
+
+    def unik_encode(self, keys, k, flags, taxids=None, taxid_bytes=0, out=None):
+        """the body unik::Writer writes for these records, as uint8.  Without `out` it is sized by unik_encode_bound."""
+        pk, n, k1 = _ptr(keys, np.uint64)
+        pt, nt, k2 = _ptr(taxids, np.uint32)
+        assert taxids is None or nt == n
+        if out is None:
+            out = _empty_like_kind(keys, unik_encode_bound(n, k, flags, taxid_bytes), np.uint8)
+        po, cap, _ = _ptr(out, np.uint8)
+        m = C.c_uint64()
+        _check(self.L.ukm_unik_encode(self.h, pk, pt, n, int(k), int(flags), int(taxid_bytes), po, cap if n else 0, C.byref(m)), m.value)
+        return out[: m.value]
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):

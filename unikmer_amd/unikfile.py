@@ -1,0 +1,93 @@
+"""`.unik` files for the Python user: the header is read and written here, the body goes through the device codec
+(Context.unik_decode / unik_encode).  gzip inflate and deflate are the `gzip` module's: one host thread.
+
+The header layout is the one unikmer_amd/host/unik.hpp states (unik::Reader::read_header, unik::Writer::write_header),
+big-endian throughout:
+    magic ".unikmer" (8) | main = 5, minor = 0, K, 0 (4 x u8) | flag u32 | number u64 | global taxid u32
+    | taxid bytes u8, 3 x 0 | description length u32 | description | scale u32 | max hash u64 | 52 reserved zero bytes
+"""
+import gzip
+import struct
+
+import numpy as np
+
+from . import lib
+
+MAGIC = b".unikmer"
+COMPACT, CANONICAL, SORTED, INCLUDE_TAXID, HASHED, SCALED = 1, 2, 4, 8, 16, 32
+UNKNOWN_NUMBER = 0xFFFFFFFFFFFFFFFF
+
+
+def _open(path):
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    return gzip.open(path, "rb") if gz else open(path, "rb")
+
+
+def _must(f, n, path):
+    b = f.read(n)
+    if len(b) != n:
+        raise ValueError("unexpected EOF: %s" % path)
+    return b
+
+
+def _read_header(f, path):
+    if f.read(8) != MAGIC:
+        raise ValueError("invalid binary format: %s" % path)
+    main, minor, k, _ = struct.unpack(">4B", _must(f, 4, path))
+    if main != 5:
+        raise ValueError("version mismatch (need v5.x): %s" % path)
+    flag, number, global_taxid, tb = struct.unpack(">IQIB3x", _must(f, 20, path))
+    if not 1 <= tb <= 4:
+        raise ValueError("bad taxid byte length: %s" % path)
+    (dl,) = struct.unpack(">I", _must(f, 4, path))
+    if dl > 1024:
+        raise ValueError("description too long: %s" % path)
+    desc = _must(f, dl, path)
+    scale, max_hash = struct.unpack(">IQ", _must(f, 12, path))
+    _must(f, 52, path)
+    return {"main_version": main, "minor_version": minor, "k": k, "flag": flag, "number": number, "global_taxid": global_taxid,
+            "taxid_bytes": tb, "description": desc.decode("latin-1"), "scale": scale, "max_hash": max_hash}
+
+
+def read_header(path):
+    """the fields of unik::Header, as a dict"""
+    with _open(path) as f:
+        return _read_header(f, path)
+
+
+def header_bytes(h):
+    desc = h.get("description", "").encode("latin-1")
+    return (MAGIC + struct.pack(">4B", h.get("main_version", 5), h.get("minor_version", 0), h["k"], 0)
+            + struct.pack(">IQIB3x", h["flag"], h.get("number", UNKNOWN_NUMBER), h.get("global_taxid", 0), h.get("taxid_bytes", 4))
+            + struct.pack(">I", len(desc)) + desc + struct.pack(">IQ", h.get("scale", 1), h.get("max_hash", UNKNOWN_NUMBER)) + bytes(52))
+
+
+def load(ctx, path, device=True, ignore_taxid=False):
+    """(header, keys, taxids): the records of a file, decoded on the device.  device=True: torch tensors on the GPU (the
+    body is uploaded, 3-6 bytes a record for a sorted file), else numpy arrays.  taxids is None when the records carry none
+    (a global taxid is in the header) or with ignore_taxid."""
+    with _open(path) as f:
+        h = _read_header(f, path)
+        body = np.frombuffer(f.read(), dtype=np.uint8)
+    if device:
+        import torch
+        body = torch.from_numpy(body.copy()).cuda()
+    keys, taxids = ctx.unik_decode(body, h["k"], h["flag"], h["taxid_bytes"], with_taxids=not ignore_taxid)
+    return h, keys, taxids
+
+
+def save(ctx, path, header, keys, taxids=None, compress=True):
+    """writes header and records; header["flag"] decides the layout (SORTED: keys must ascend pair by pair).  `number` is
+    set to the record count."""
+    h = dict(header)
+    n = int(keys.numel()) if lib._is_torch(keys) else len(keys)
+    h["number"] = n
+    if taxids is None:
+        h["flag"] &= ~INCLUDE_TAXID
+    body = ctx.unik_encode(keys, h["k"], h["flag"], taxids=taxids, taxid_bytes=h.get("taxid_bytes", 4))
+    if lib._is_torch(body):
+        body = body.cpu().numpy()
+    with (gzip.open(path, "wb", compresslevel=6) if compress else open(path, "wb")) as f:
+        f.write(header_bytes(h))
+        f.write(body.tobytes())
