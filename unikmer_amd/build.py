@@ -95,8 +95,8 @@ CLI = os.path.join(HERE, "bin", "unikmer")
 
 def build_cli(force=False, verbose=False):
     """the `unikmer`-compatible C++ driver (host side of the drop-in), linked against the C ABI"""
-    srcs = [os.path.join(HOST, "main.cpp"), os.path.join(HOST, "unik.hpp"),
-            os.path.join(HERE, "..", "include", "unikmer_hip.h")]
+    # one translation unit, main.cpp, that includes the other files of host/: every one of them is a dependency
+    srcs = [os.path.join(HOST, f) for f in sorted(os.listdir(HOST))] + [os.path.join(HERE, "..", "include", "unikmer_hip.h")]
     if not (force or _stale(CLI, srcs + [SO])):
         return CLI
     os.makedirs(os.path.dirname(CLI), exist_ok=True)
