@@ -55,7 +55,7 @@ extern "C" {
 #define UKM_ERR_CAPACITY (-7)     /* out_cap too small; *n_out holds the required size */
 #define UKM_ERR_K (-8)            /* k out of range (1..32 codes, 1..64 hashes; count.go:81-87) */
 #define UKM_ERR_PEER (-9)         /* a collective call: another rank reported a failure; no rank went on (see that rank) */
-#define UKM_ERR_FORMAT (-10)      /* a .unik body ends inside a record (unik.hpp: "truncated record", "unexpected EOF") */
+#define UKM_ERR_FORMAT (-10)      /* a .unik body ends inside a record (unik.hpp: "truncated record", "unexpected EOF"); a line outside ukm_dump's grammar */
 
 /* scan / merge modes: sort.go:484-572 (-u / -d / plain), util-sort.go:35-190 (chunk protocol) */
 #define UKM_PLAIN 0
@@ -440,6 +440,47 @@ int ukm_unik_decode(ukm_ctx *ctx, const uint8_t *body, uint64_t n_bytes, int k, 
 int ukm_unik_encode(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint64_t n, int k, uint32_t flags,
                     int taxid_bytes, uint8_t *out_bytes, uint64_t out_cap, uint64_t *n_out);
 uint64_t ukm_unik_encode_bound(uint64_t n, int k, uint32_t flags, int taxid_bytes);
+
+/* ---- k-mer text: replace the record loop of view.go:163-218 (everything except -g) and the line loop of dump.go:128-315
+ *      (the paths that do not hash).  Byte buffers need no alignment; out_cap and *n_out of ukm_view are in BYTES; the size
+ *      query, UKM_ERR_CAPACITY (with the exact size, and no output pass has run) and n == 0 / n_bytes == 0 as everywhere.
+ *      view: the text `unikmer view` prints for the records, line by line.  The fields of a line: C = the code as an unsigned
+ *      decimal without padding; T = the record's taxid, the same way (taxids == NULL: every record carries file_taxid, as in
+ *      ukm_grep); K = with hashed == 0 k letters, letter i from the left "ACGT"[(code >> 2(k-1-i)) & 3] (bits above 2k are
+ *      ignored), with hashed != 0 the same as C; Q = k times 'g', also when hashed.  k: 1..32 when hashed == 0, 1..64
+ *      otherwise (UKM_ERR_K).  An unknown format, or UKM_VIEW_WITH_TAXID on a format other than FASTA / FASTQ: UKM_ERR_INVALID.
+ *      ukm_view_bound is pure host code: exact for UKM_VIEW_KMER with hashed == 0, n (k + 1); else the worst case of 20 and
+ *      10 digits.  All offsets are 64-bit (1e8 FASTA records are more than 4 GB).
+ *      dump: the records of k-mer text, in line order.  The grammar is strict.  A line is the bytes between two LF, the
+ *      last may lack its LF; one trailing CR is dropped; an empty line gives no record; every other line is field1 or, with
+ *      UKM_DUMP_TAXID, field1 TAB field2, and nothing else.  field1: exactly k bytes, k in 1..32 (UKM_ERR_K), each one of
+ *      A N M V H R D W (-> 0), C S B Y (-> 1), G K (-> 2), T U (-> 3) in either case; with UKM_DUMP_DECIMAL 1..20 digits with a
+ *      value <= 2^64 - 1.  field2: 1..10 digits with a value <= 2^32 - 1.  A line that does not fit (a wrong length, another
+ *      byte, a space, a TAB without the flag, none with it, a second TAB, a sign, too many digits, an overflow) gives
+ *      UKM_ERR_FORMAT, and *bad_off (may be NULL; written in this case only) is the byte offset at which the first such line
+ *      starts.  That is decided in the counting pass: it wins over UKM_ERR_CAPACITY.  UKM_DUMP_CANONICAL: code -> min(code,
+ *      revcomp(code, k)); UKM_DUMP_CANONICAL_ONLY (wins over the former): a line whose code is not its own canonical form
+ *      gives no record; either with UKM_DUMP_DECIMAL: UKM_ERR_INVALID.  out_taxids may be NULL: the second column is still
+ *      checked, but not stored.  The number of LF + 1 bounds the number of records.
+ *      After either call ukm_last_kernel_ms reports the scan between the two passes over the data (its launches and the
+ *      read-back of the size), ukm_last_call_ms the whole call; the fixed-width view has one pass and no scan. */
+#define UKM_VIEW_KMER 0u         /* K\n            view     */
+#define UKM_VIEW_KMER_CODE 1u    /* K\tC\n         view -n  */
+#define UKM_VIEW_CODE 2u         /* C\n            view -N  */
+#define UKM_VIEW_KMER_TAXID 3u   /* K\tT\n         view -t  */
+#define UKM_VIEW_TAXID 4u        /* T\n            view -T  */
+#define UKM_VIEW_FASTA 5u        /* >C\nK\n        view -a  */
+#define UKM_VIEW_FASTQ 6u        /* @C\nK\n+\nQ\n  view -q  */
+#define UKM_VIEW_WITH_TAXID 16u  /* FASTA / FASTQ only: the header line is ">C T" / "@C T" (view -a -t, -q -t) */
+int ukm_view(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, uint32_t file_taxid, uint64_t n, int k, int hashed,
+             uint32_t format, uint8_t *out_bytes, uint64_t out_cap, uint64_t *n_out);
+uint64_t ukm_view_bound(uint64_t n, int k, int hashed, uint32_t format);
+#define UKM_DUMP_TAXID 1u          /* two columns: field1 TAB taxid */
+#define UKM_DUMP_DECIMAL 2u        /* field1 is a decimal uint64 (dump --hashed); k is ignored */
+#define UKM_DUMP_CANONICAL 4u      /* dump -K */
+#define UKM_DUMP_CANONICAL_ONLY 8u /* dump -O */
+int ukm_dump(ukm_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int k, uint32_t flags, uint64_t *out_keys,
+             uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out, uint64_t *bad_off);
 
 /* ---- k-way merge: replaces mergeChunksFile (util-sort.go:227-606).  Streams are expected
  *      to be sorted (chunk files); an unsorted one is tolerated (the call then sorts the

@@ -1,7 +1,43 @@
 // cmd_cpu.hpp — the commands that need no GPU: view, dump, num, info/stats, concat, head, encode, decode
 // (view -g and the -H forms of dump / encode hash on the device)
+// Where there is a device, dump without -H parses its text with ukm_dump and -- under UNIKMER_DEVICE_TEXT=1: a small file is
+// printed sooner without a context, DESIGN.md 4.18 -- view without -g renders its text with ukm_view (records.hpp: text_ctx).
+// The host loops below are what runs without a device, under UNIKMER_HOST_TEXT=1, and for dump whenever a line is outside
+// ukm_dump's strict grammar: they define what both commands print, read and say.
 #pragma once
 #include "records.hpp"
+
+// the format of `view`'s flags, in the precedence of the host loop: -a > -q > -t > -T > -N > -n > plain
+static u32 view_format(const Args &a) {
+    const u32 t = a.has("show-taxid") ? UKM_VIEW_WITH_TAXID : 0u;
+    if (a.has("fasta")) return UKM_VIEW_FASTA | t;
+    if (a.has("fastq")) return UKM_VIEW_FASTQ | t;
+    if (a.has("show-taxid")) return UKM_VIEW_KMER_TAXID;
+    if (a.has("show-taxid-only")) return UKM_VIEW_TAXID;
+    if (a.has("show-code-only")) return UKM_VIEW_CODE;
+    if (a.has("show-code")) return UKM_VIEW_KMER_CODE;
+    return UKM_VIEW_KMER;
+}
+// One file through ukm_view, in chunks of records that bound the text buffer.  What is printed as a record's taxid is what
+// unik::Reader::read hands out: its own, else the header's global taxid -- also under -I, which the loader is not told about.
+static void view_on_device(ukm_ctx *c, bool own, const string &file, const Options &o, u32 fmt, unik::OutStream &out) {
+    Options ol = o;
+    ol.ignore_taxid = false;
+    const Loaded L = load_unik(file, ol);
+    const int k = L.h.k, hashed = L.h.is_hashed() ? 1 : 0;
+    const u64 n = L.codes.size(), chunk = std::max<u64>(1, (256ull << 20) / ukm_view_bound(1, k, hashed, fmt));
+    if (!n) return;
+    const u64 cap = ukm_view_bound(std::min(n, chunk), k, hashed, fmt);
+    std::unique_ptr<uint8_t[]> text(new uint8_t[cap]);
+    for (u64 i = 0; i < n; i += chunk) {
+        const u64 m = std::min(chunk, n - i);
+        u64 bytes = 0;
+        ck(ukm_view(c, L.codes.data() + i, L.h.is_include_taxid() ? L.taxids.data() + i : nullptr, L.h.global_taxid, m, k, hashed, fmt,
+                    text.get(), cap, &bytes));
+        out.write(text.get(), bytes);
+    }
+    if (own) ck(ukm_ctx_trim(c));
+}
 
 static int cmd_view(int argc, char **argv) {  // view.go:163-218
     Args a = parse_args(argc, argv, {{'o', "out-file", true}, {'n', "show-code", false}, {'N', "show-code-only", false}, {'a', "fasta", false},
@@ -41,7 +77,10 @@ static int cmd_view(int argc, char **argv) {  // view.go:163-218
         ck(ukm_sort_pairs(gpu->c, gh.data(), gpos.data(), nw, 64));
         info("%llu hash-k-mers pairs from %llu sequences loaded", (unsigned long long)nw, (unsigned long long)nrec);
     };
+    bool text_own = false;
+    ukm_ctx *text_c = genomes.empty() ? text_ctx(o, o.device_view, &text_own) : nullptr;  // (with -g the host loop, also where -g is ignored)
     for (auto &f : files) {
+        if (text_c) { view_on_device(text_c, text_own, f, o, view_format(a), *out); continue; }
         unik::Reader r(f);
         const int k = r.h.k;
         const bool hashed = r.h.is_hashed();
@@ -102,6 +141,57 @@ static int cmd_view(int argc, char **argv) {  // view.go:163-218
     return 0;
 }
 
+// The texts of `dump` through ukm_dump: false when a line is outside its grammar (or there is nothing it could be asked: no
+// line, a k it does not take) -- nothing has been written then, and the host loop runs over the same texts.  k and whether
+// there are two columns come from the first non-empty line, as in the host loop; -u is applied here, first occurrences kept.
+static bool dump_on_device(ukm_ctx *c, bool own, const vector<string> &texts, bool decimal, bool canonical, bool canonical_only, bool unique,
+                           int &k, bool &include_taxid, vector<u64> &codes, vector<u32> &taxids) {
+    bool found = false;
+    for (auto &t : texts) {
+        std::istringstream ss(t);
+        string line;
+        while (!found && std::getline(ss, line)) {
+            trim_line_end(line);
+            if (line.empty()) continue;
+            const size_t tab = line.find_first_of("\t ");
+            if (!decimal) k = (int)(tab == string::npos ? line.size() : tab);
+            include_taxid = tab != string::npos;
+            found = true;
+        }
+        if (found) break;
+    }
+    if (!found || k < 1 || k > (decimal ? 64 : 32)) return false;
+    const u32 flags = (include_taxid ? UKM_DUMP_TAXID : 0u) | (decimal ? UKM_DUMP_DECIMAL : 0u) |
+                      (!decimal && canonical ? UKM_DUMP_CANONICAL : 0u) | (!decimal && canonical_only ? UKM_DUMP_CANONICAL_ONLY : 0u);
+    u64 n = 0;
+    for (auto &t : texts) {
+        const u64 cap = (u64)std::count(t.begin(), t.end(), '\n') + 1;
+        codes.resize(n + cap);
+        if (include_taxid) taxids.resize(n + cap);
+        u64 m = 0;
+        const int rc = ukm_dump(c, (const uint8_t *)t.data(), t.size(), k, flags, codes.data() + n, include_taxid ? taxids.data() + n : nullptr,
+                                cap, &m, nullptr);
+        if (rc == UKM_ERR_FORMAT) return false;
+        ck(rc);
+        n += m;
+    }
+    if (own) ck(ukm_ctx_trim(c));
+    if (unique) {
+        std::set<u64> seen;
+        u64 kept = 0;
+        for (u64 i = 0; i < n; i++) {
+            if (!seen.insert(codes[i]).second) continue;
+            codes[kept] = codes[i];
+            if (include_taxid) taxids[kept] = taxids[i];
+            kept++;
+        }
+        n = kept;
+    }
+    codes.resize(n);
+    if (include_taxid) taxids.resize(n);
+    return true;
+}
+
 static int cmd_dump(int argc, char **argv) {  // dump.go:128-315
     Args a = parse_args(argc, argv, {{'o', "out-prefix", true}, {'u', "unique", false}, {'K', "canonical", false}, {'O', "canonical-only", false},
                                      {'s', "sorted", false}, {'t', "taxid", true}, {'H', "hash", false}, {0, "hashed", false}, {'k', "kmer-len", true}});
@@ -123,8 +213,38 @@ static int cmd_dump(int argc, char **argv) {  // dump.go:128-315
     bool include_taxid = false;
     vector<string> hk;  // -H: the k-mers of all files, hashed on the device after the last line
     vector<u32> ht;
-    for (auto &f : files) {
-        std::istringstream ss(read_text(f));
+    // the first line fixes k and whether taxids are included (dump.go:139-223)
+    auto open_writer = [&]() {
+        u32 mode = 0;
+        if (sorted) mode |= unik::UnikSorted;
+        else if (o.compact && !hashed_already && !hashed) mode |= unik::UnikCompact;
+        if (canonical || canonical_only) mode |= unik::UnikCanonical;
+        if (include_taxid) mode |= unik::UnikIncludeTaxID;
+        if (hashed_already || hashed) mode |= unik::UnikHashed;
+        w.reset(new unik::Writer(os, k, mode));
+        w->set_max_taxid(o.max_taxid);
+        if (gtaxid && !include_taxid) w->set_global_taxid(gtaxid);
+    };
+    vector<string> texts;  // read once: the device path and the host loop behind it see the same bytes (a file may be stdin)
+    for (auto &f : files) texts.push_back(read_text(f));
+    bool text_own = false;
+    ukm_ctx *text_c = hashed ? nullptr : text_ctx(o, o.device_dump, &text_own);
+    if (text_c) {
+        vector<u64> dc;
+        vector<u32> dt;
+        int dk = k;
+        bool dtax = false;
+        if (dump_on_device(text_c, text_own, texts, hashed_already, canonical, canonical_only, unique, dk, dtax, dc, dt)) {
+            k = dk;
+            include_taxid = dtax;
+            open_writer();
+            write_records(*w, o, dc.data(), dt.data(), dc.size());
+            n = dc.size();
+            texts.clear();
+        }
+    }
+    for (auto &text : texts) {
+        std::istringstream ss(text);
         string line;
         while (std::getline(ss, line)) {
             trim_line_end(line);
@@ -134,20 +254,12 @@ static int cmd_dump(int argc, char **argv) {  // dump.go:128-315
             size_t tab = line.find_first_of("\t ");
             bool has_t = false;
             if (tab != string::npos) { kmer = line.substr(0, tab); taxid = (u32)strtoul(line.c_str() + tab + 1, nullptr, 10); has_t = true; }
-            if (!w) {  // the first line fixes k and whether taxids are included (dump.go:139-223)
+            if (!w) {
                 if (!hashed_already) k = (int)kmer.size();
                 if (k > 32 && !hashed_already && !hashed) die("k-mer size (%d) should be <= 32", k);
                 if (k > 64) die("k-mer size (%d) should be <= 64", k);
                 include_taxid = has_t;
-                u32 mode = 0;
-                if (sorted) mode |= unik::UnikSorted;
-                else if (o.compact && !hashed_already && !hashed) mode |= unik::UnikCompact;
-                if (canonical || canonical_only) mode |= unik::UnikCanonical;
-                if (include_taxid) mode |= unik::UnikIncludeTaxID;
-                if (hashed_already || hashed) mode |= unik::UnikHashed;
-                w.reset(new unik::Writer(os, k, mode));
-                w->set_max_taxid(o.max_taxid);
-                if (gtaxid && !include_taxid) w->set_global_taxid(gtaxid);
+                open_writer();
             }
             u64 code;
             if (hashed) {

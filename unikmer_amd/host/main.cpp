@@ -18,8 +18,11 @@
 //                          records in input order with their own taxids; grep -s/-u/-d -> ukm_sort_* -> ukm_unique
 //                   rfilter (rfilter.go)  nodes.dmp with ranks + rank file -> ukm_taxonomy_set_ranks; per input file ukm_rfilter
 //                   tsplit  (tsplit.go)   the files' records with their taxids -> ukm_tsplit -> one .unik per taxid
-//   cmd_cpu.hpp     CPU-only commands (no GPU needed): view, dump, num, info/stats, concat, head, encode, decode
-// .unik bodies are decoded and encoded by ukm_unik_decode / ukm_unik_encode (records.hpp) unless UNIKMER_HOST_CODEC=1.
+//   cmd_cpu.hpp     commands that need no GPU: view, dump, num, info/stats, concat, head, encode, decode; where there is one,
+//                          dump (without -H) parses its text with ukm_dump and view (without -g, under UNIKMER_DEVICE_TEXT=1)
+//                          renders its text with ukm_view
+// .unik bodies are decoded and encoded by ukm_unik_decode / ukm_unik_encode (records.hpp) unless UNIKMER_HOST_CODEC=1;
+// UNIKMER_HOST_TEXT=1 keeps view and dump on their host loops.
 // Not implemented (SURVEY.md §2a out of scope): grep -m/-O/-S/--force, rfilter's built-in default rank list,
 // map -x/-X/--circular, autocompletion; count -S (syncmer sketch: third-party rule not reconstructable from the tree).
 #include "cmd_chunks.hpp"

@@ -12,10 +12,14 @@
 // UNIKMER_HOST_CODEC=1 keeps the host codec of unik.hpp everywhere (the comparison path of the tests and of the measurement),
 // UNIKMER_DEVICE_CODEC=1 asks for the device codec whatever the default.
 static const bool DEVICE_CODEC_DEFAULT = true;
+// The same switch for the text of `view` (ukm_view) and `dump` (ukm_dump), one default per command;
+// UNIKMER_HOST_TEXT=1 keeps the host loops of cmd_cpu.hpp, UNIKMER_DEVICE_TEXT=1 asks for the device path in both.
+static const bool DEVICE_VIEW_DEFAULT = false, DEVICE_DUMP_DEFAULT = true;
 struct Options {
     bool compress = true, compact = false, ignore_taxid = false, skip_file_check = false;
     int level = -1, gpu = 0;
     bool device_codec = DEVICE_CODEC_DEFAULT;  // .unik bodies through ukm_unik_decode / ukm_unik_encode (load_unik, write_unik)
+    bool device_view = DEVICE_VIEW_DEFAULT, device_dump = DEVICE_DUMP_DEFAULT;  // view / dump text through ukm_view / ukm_dump
     u32 max_taxid = 0xFFFFFFFFu;
     string data_dir;
 };
@@ -36,6 +40,9 @@ static Options get_options(const Args &a) {
     const char *hc = getenv("UNIKMER_HOST_CODEC"), *dc = getenv("UNIKMER_DEVICE_CODEC");
     if (dc && dc[0] == '1') o.device_codec = true;
     if (hc && hc[0] == '1') o.device_codec = false;
+    const char *ht = getenv("UNIKMER_HOST_TEXT"), *dt = getenv("UNIKMER_DEVICE_TEXT");
+    if (dt && dt[0] == '1') o.device_view = o.device_dump = true;
+    if (ht && ht[0] == '1') o.device_view = o.device_dump = false;
     return o;
 }
 // util-cli.go:192-264 : files from the command line plus the optional list file; "-" = stdin
@@ -96,6 +103,16 @@ static ukm_ctx *codec_ctx(const Options &o, bool *own) {
     }
     *own = mine != nullptr;
     return mine;
+}
+
+// The context ukm_view / ukm_dump run on: codec_ctx's, whatever is said about the codec.  nullptr: the host loops run -- they
+// were asked for, or this machine has no device (view and dump stay usable there).
+static ukm_ctx *text_ctx(const Options &o, bool wanted, bool *own) {
+    *own = false;
+    if (!wanted) return nullptr;
+    Options oc = o;
+    oc.device_codec = true;
+    return codec_ctx(oc, own);
 }
 
 // ---- taxonomy (util.go:119-171): nodes.dmp (+ merged.dmp) -> ukm_taxonomy_load ---------------------

@@ -16,8 +16,12 @@ SO_PATH = os.environ.get("UKM_LIB_PATH") or os.path.join(_HERE, "libunikmer_hip.
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_ILLEGAL_BASE = -1, -2, -3, -4
 ERR_UNSORTED, ERR_NO_TAXONOMY, ERR_CAPACITY, ERR_K, ERR_PEER = -5, -6, -7, -8, -9
-ERR_FORMAT = -10   # a .unik body ends inside a record
+ERR_FORMAT = -10   # a .unik body ends inside a record; a line of k-mer text outside the grammar of ukm_dump
 UNIK_COMPACT, UNIK_SORTED, UNIK_INCLUDE_TAXID = 1, 4, 8   # header flag bits the .unik codec looks at (unik.hpp)
+# ukm_view formats and ukm_dump flags (include/unikmer_hip.h: UKM_VIEW_*, UKM_DUMP_*)
+VIEW_KMER, VIEW_KMER_CODE, VIEW_CODE, VIEW_KMER_TAXID, VIEW_TAXID, VIEW_FASTA, VIEW_FASTQ = range(7)
+VIEW_WITH_TAXID = 16
+DUMP_TAXID, DUMP_DECIMAL, DUMP_CANONICAL, DUMP_CANONICAL_ONLY = 1, 2, 4, 8
 PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 F_MIX_TAXID, F_CMP_TAXID = 2, 4
@@ -42,6 +46,7 @@ SYMBOLS = [
     "ukm_locate", "ukm_map", "ukm_map_gapped", "ukm_grep", "ukm_filter", "ukm_sample",
     "ukm_taxonomy_set_ranks", "ukm_rank_filter_plan", "ukm_rank_pass", "ukm_rfilter", "ukm_tsplit",
     "ukm_unik_decode", "ukm_unik_encode", "ukm_unik_encode_bound",
+    "ukm_view", "ukm_view_bound", "ukm_dump",
 ]
 
 
@@ -90,7 +95,9 @@ class UnsortedError(UkmError):
 
 
 class FormatError(UkmError):
-    """a .unik body ends inside a record (UKM_ERR_FORMAT)"""
+    """a .unik body ends inside a record, or a line of k-mer text is outside the grammar of ukm_dump (UKM_ERR_FORMAT);
+    bad_off: the byte offset at which that line starts (ukm_dump only)"""
+    bad_off = None
 
 
 class CapacityError(UkmError):
@@ -182,6 +189,10 @@ def load():
     L.ukm_unik_encode.argtypes = [vp, vp, vp, u64, i32, u32, i32, vp, u64, pu64]
     L.ukm_unik_encode_bound.argtypes = [u64, i32, u32, i32]
     L.ukm_unik_encode_bound.restype = u64
+    L.ukm_view.argtypes = [vp, vp, vp, u32, u64, i32, i32, u32, vp, u64, pu64]
+    L.ukm_view_bound.argtypes = [u64, i32, i32, u32]
+    L.ukm_view_bound.restype = u64
+    L.ukm_dump.argtypes = [vp, vp, u64, i32, u32, vp, vp, u64, pu64, pu64]
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -275,6 +286,11 @@ def _empty_like_kind(ref, n, dtype):
 def unik_encode_bound(n, k, flags, taxid_bytes=0):
     """bytes a .unik body of n records takes at most (exact for the unsorted layouts); pure host code"""
     return int(load().ukm_unik_encode_bound(int(n), int(k), int(flags), int(taxid_bytes)))
+
+
+def view_bound(n, k, hashed=False, fmt=VIEW_KMER):
+    """bytes the text of n records takes at most (exact for VIEW_KMER of codes that are not hashed); pure host code"""
+    return int(load().ukm_view_bound(int(n), int(k), int(bool(hashed)), int(fmt)))
 
 
 class Context:
@@ -679,6 +695,55 @@ class Context:
         m = C.c_uint64()
         _check(self.L.ukm_unik_encode(self.h, pk, pt, n, int(k), int(flags), int(taxid_bytes), po, cap if n else 0, C.byref(m)), m.value)
         return out[: m.value]
+
+    # ---- k-mer text (`unikmer view` / `unikmer dump`) ----
+    def view(self, keys, taxids=None, file_taxid=0, *, k, hashed=False, fmt=VIEW_KMER, out=None):
+        """the text `unikmer view` prints for the records, as uint8 where the inputs live.  taxids None: every record carries
+        file_taxid.  Without `out` the size is asked for first (the size query; VIEW_KMER of plain codes is n (k + 1))."""
+        pk, n, k1 = _ptr(keys, np.uint64)
+        pt, nt, k2 = _ptr(taxids, np.uint32)
+        assert taxids is None or nt == n
+        args = (int(file_taxid), n, int(k), int(bool(hashed)), int(fmt))
+        m = C.c_uint64()
+        if out is None:
+            rc = self.L.ukm_view(self.h, pk, pt, *args, None, 0, C.byref(m))
+            if rc != ERR_CAPACITY:
+                _check(rc)
+            out = _empty_like_kind(keys, m.value, np.uint8)
+        po, cap, _ = _ptr(out, np.uint8)
+        _check(self.L.ukm_view(self.h, pk, pt, *args, po, cap if n else 0, C.byref(m)), m.value)
+        return out[: m.value]
+
+    def dump(self, text, *, k, flags=0, out=None, out_taxids=None):
+        """the records of k-mer text (`unikmer dump`, the strict grammar of include/unikmer_hip.h): (keys, taxids), taxids None
+        without DUMP_TAXID.  Without `out` the number of records is asked for first.  A line outside the grammar: FormatError
+        with bad_off."""
+        pb, nb, k1 = _ptr(text, np.uint8)
+        tax = bool(flags & DUMP_TAXID)
+        n, bad = C.c_uint64(), C.c_uint64()
+
+        def call(po, pot, cap):
+            rc = self.L.ukm_dump(self.h, pb, nb, int(k), int(flags), po, pot, cap, C.byref(n), C.byref(bad))
+            if rc == ERR_FORMAT:
+                try:
+                    _check(rc)
+                except FormatError as e:
+                    e.bad_off = bad.value
+                    raise
+            return rc
+        if out is None:
+            rc = call(None, None, 0)
+            if rc != ERR_CAPACITY:
+                _check(rc)
+            out = _empty_like_kind(text, n.value, np.uint64)
+        po, cap, _ = _ptr(out, np.uint64)
+        if tax and out_taxids is None:
+            out_taxids = _empty_like_kind(text, cap, np.uint32)
+        pot, ncap, _ = _ptr(out_taxids if tax else None, np.uint32)
+        if tax:
+            cap = min(cap, ncap)
+        _check(call(po, pot, cap if nb else 0), n.value)
+        return out[: n.value], (out_taxids[: n.value] if tax else None)
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
