@@ -441,6 +441,29 @@ int ukm_unik_encode(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxids, 
                     int taxid_bytes, uint8_t *out_bytes, uint64_t out_cap, uint64_t *n_out);
 uint64_t ukm_unik_encode_bound(uint64_t n, int k, uint32_t flags, int taxid_bytes);
 
+/* ---- deflate: replace the gzip writer behind a .unik body (util-io.go:57-64, pgzip).  src [n_bytes] (host or device, any
+ *      alignment) becomes a byte-aligned sequence of RFC 1951 blocks, none of them final unless asked: the source is cut into
+ *      independent chunks of 32768 bytes, each one dynamic-Huffman block of literals followed by an empty stored block (the
+ *      sync-flush marker), or one stored block where that would not be smaller.  No matches are searched for: a sorted body is
+ *      delta bytes in which LZ77 finds nothing; k-mer TEXT is three times larger this way than through zlib and does not
+ *      belong here.  Fragments concatenate: the caller's stream may hold zlib's own sync-flushed output in front of one.
+ *      *crc32 is in/out: on entry the CRC-32 of the bytes that precede src in the caller's stream (0: none), on exit (UKM_OK
+ *      only) the CRC-32 of those bytes followed by src.  *n_out = the fragment's bytes; out == NULL with out_cap == 0 is the
+ *      size query; too small an out_cap: UKM_ERR_CAPACITY with the need, and nothing has been written to out.  Nothing
+ *      outside out[0, *n_out) is ever written.  The output is a pure function of src and flags.  n_bytes == 0: an empty
+ *      fragment, or just what the flags add.  UKM_DEFLATE_GZIP with *crc32 != 0 on entry: UKM_ERR_INVALID.
+ *      ukm_deflate_bound (pure host code, never exceeded): n_bytes + 5 per chunk, + 2 with FINAL, + 20 with GZIP.
+ *      ukm_crc32_combine (pure host code): the CRC-32 of A followed by B from crc(A), crc(B) and B's length, as zlib's
+ *      crc32_combine; the library does not link zlib.
+ *      After a call ukm_last_kernel_ms reports the scan between the two passes over the data (its launches and the two
+ *      read-backs), ukm_last_call_ms the whole call. */
+#define UKM_DEFLATE_FINAL 1u /* append the final empty block: the fragment then ends the deflate stream */
+#define UKM_DEFLATE_GZIP 2u  /* implies FINAL: 10-byte gzip header in front, CRC-32 and ISIZE behind: a complete member */
+int ukm_deflate(ukm_ctx *ctx, const uint8_t *src, uint64_t n_bytes, uint32_t flags, uint8_t *out, uint64_t out_cap,
+                uint64_t *n_out, uint32_t *crc32);
+uint64_t ukm_deflate_bound(uint64_t n_bytes, uint32_t flags);
+uint32_t ukm_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* ---- k-mer text: replace the record loop of view.go:163-218 (everything except -g) and the line loop of dump.go:128-315
  *      (the paths that do not hash).  Byte buffers need no alignment; out_cap and *n_out of ukm_view are in BYTES; the size
  *      query, UKM_ERR_CAPACITY (with the exact size, and no output pass has run) and n == 0 / n_bytes == 0 as everywhere.

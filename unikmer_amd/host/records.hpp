@@ -15,11 +15,17 @@ static const bool DEVICE_CODEC_DEFAULT = true;
 // The same switch for the text of `view` (ukm_view) and `dump` (ukm_dump), one default per command;
 // UNIKMER_HOST_TEXT=1 keeps the host loops of cmd_cpu.hpp, UNIKMER_DEVICE_TEXT=1 asks for the device path in both.
 static const bool DEVICE_VIEW_DEFAULT = false, DEVICE_DUMP_DEFAULT = true;
+// And for the gzip of a .unik OUTPUT (write_unik, write_following): the body is deflated on the device (ukm_deflate: Huffman
+// coding in independent chunks) and only the compressed bytes are downloaded, where the device codec is on.
+// UNIKMER_DEVICE_GZIP=1 asks for it, UNIKMER_HOST_GZIP=1 keeps zlib everywhere.  --compression-level 0, text outputs and the
+// commands without a device (num, info, concat, head) stay on zlib whatever is said.
+static const bool DEVICE_GZIP_DEFAULT = false;
 struct Options {
     bool compress = true, compact = false, ignore_taxid = false, skip_file_check = false;
     int level = -1, gpu = 0;
     bool device_codec = DEVICE_CODEC_DEFAULT;  // .unik bodies through ukm_unik_decode / ukm_unik_encode (load_unik, write_unik)
     bool device_view = DEVICE_VIEW_DEFAULT, device_dump = DEVICE_DUMP_DEFAULT;  // view / dump text through ukm_view / ukm_dump
+    bool device_gzip = DEVICE_GZIP_DEFAULT;    // compressed .unik outputs through ukm_deflate (write_unik, write_following)
     u32 max_taxid = 0xFFFFFFFFu;
     string data_dir;
 };
@@ -43,6 +49,9 @@ static Options get_options(const Args &a) {
     const char *ht = getenv("UNIKMER_HOST_TEXT"), *dt = getenv("UNIKMER_DEVICE_TEXT");
     if (dt && dt[0] == '1') o.device_view = o.device_dump = true;
     if (ht && ht[0] == '1') o.device_view = o.device_dump = false;
+    const char *hg = getenv("UNIKMER_HOST_GZIP"), *dg = getenv("UNIKMER_DEVICE_GZIP");
+    if (dg && dg[0] == '1') o.device_gzip = true;
+    if (hg && hg[0] == '1') o.device_gzip = false;
     return o;
 }
 // util-cli.go:192-264 : files from the command line plus the optional list file; "-" = stdin
@@ -288,6 +297,22 @@ static void write_records(unik::Writer &w, const Options &o, const u64 *codes, c
     bool own = false;
     ukm_ctx *c = n ? codec_ctx(o, &own) : nullptr;
     if (c && w.h.is_compact() && !w.h.is_sorted() && (w.h.k < 1 || w.h.k > 32)) c = nullptr;
+    if (c && w.device_gzip()) {
+        // encoded into a device buffer and deflated there: the body never crosses to the host uncompressed
+        const u64 bound = ukm_unik_encode_bound(n, w.h.k, w.h.flag, w.h.taxid_bytes);
+        DevMem body(c, bound);
+        u64 m = 0, nf = 0;
+        const int rc = ukm_unik_encode(c, codes, tx ? taxids : nullptr, n, w.h.k, w.h.flag, w.h.taxid_bytes, (uint8_t *)body.p, bound, &m);
+        if (rc == UKM_ERR_UNSORTED) throw unik::Error("codes written to a sorted .unik must be ascending");
+        ck(rc);
+        const u64 fbound = ukm_deflate_bound(m, 0);
+        std::unique_ptr<uint8_t[]> frag(new uint8_t[fbound]);
+        uint32_t crc = 0;
+        ck(ukm_deflate(c, (const uint8_t *)body.p, m, 0, frag.get(), fbound, &nf, &crc));
+        if (own) ck(ukm_ctx_trim(c));
+        w.write_body_deflated(frag.get(), nf, crc, m);
+        return;
+    }
     if (c) {
         const u64 bound = ukm_unik_encode_bound(n, w.h.k, w.h.flag, w.h.taxid_bytes);
         std::unique_ptr<uint8_t[]> body(new uint8_t[bound]);  // (not a vector: nothing here needs 1.7 GB of zeros first)
@@ -304,6 +329,12 @@ static void write_records(unik::Writer &w, const Options &o, const u64 *codes, c
         else w.write_code(codes[i]);
     }
 }
+// whether an output of n records is written in device-gzip mode: asked for, compressed at a level other than 0, and there is
+// a device codec to encode the body where ukm_deflate will find it
+static bool device_gzip_for(const Options &o, u64 n) {
+    bool own = false;
+    return o.compress && o.device_gzip && o.level != 0 && n && codec_ctx(o, &own) != nullptr;
+}
 static void finish_unik(unik::OutStream &os, unik::Writer &w, const Options &o, const string &out_file, const u64 *codes, const u32 *taxids, u64 n) {
     w.set_number(n);
     write_records(w, o, codes, taxids, n);
@@ -313,7 +344,7 @@ static void finish_unik(unik::OutStream &os, unik::Writer &w, const Options &o, 
 }
 static void write_unik(const string &out_file, const Options &o, int k, u32 mode, u32 max_taxid, u32 global_taxid,
                        const unik::Header *scale_from, const u64 *codes, const u32 *taxids, u64 n) {
-    unik::OutStream os(out_file, o.compress, o.level);
+    unik::OutStream os(out_file, o.compress, o.level, device_gzip_for(o, n));
     unik::Writer w(os, k, mode);
     w.set_max_taxid(max_taxid);
     if (global_taxid) w.set_global_taxid(global_taxid);
@@ -322,7 +353,7 @@ static void write_unik(const string &out_file, const Options &o, int k, u32 mode
 }
 // an output that follows an input header (filter.go:123-125, sample.go:116-122): no global taxid, the reader's taxid width
 static void write_following(const string &out_file, const Options &o, const unik::Header &h0, u32 mode, const u64 *codes, const u32 *taxids, u64 n) {
-    unik::OutStream os(out_file, o.compress, o.level);
+    unik::OutStream os(out_file, o.compress, o.level, device_gzip_for(o, n));
     unik::Writer w(os, h0.k, mode & ~(u32)unik::UnikScaled);
     w.h.taxid_bytes = h0.taxid_bytes;
     if (mode & unik::UnikScaled) w.set_scale(h0.scale, h0.max_hash);

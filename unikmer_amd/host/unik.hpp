@@ -23,6 +23,7 @@
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -106,43 +107,117 @@ class InStream {
     gzFile gz_ = nullptr;
 };
 
+// Three forms: a plain file; gzip through zlib's gz* API; and "device gzip": a plain file that holds ONE gzip member whose
+// deflate stream this class assembles -- small writes (the header, a Writer's trailing bytes) go through a raw zlib deflate
+// stream, a body that was deflated elsewhere (ukm_deflate: a byte-aligned run of blocks, none final) is appended as it is
+// behind a sync flush, and the CRC-32 runs alongside.  Header, body and trailing bytes may come in any order of calls.
 class OutStream {
   public:
-    OutStream(const std::string &path, bool compress, int level) : path_(path) {
-        if (compress) {
+    OutStream(const std::string &path, bool compress, int level, bool device_gzip = false) : path_(path) {
+        if (compress && device_gzip && level != 0) {
+            open_plain();
+            memset(&z_, 0, sizeof z_);
+            if (deflateInit2(&z_, level < 0 ? 6 : (level > 9 ? 9 : level), Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK)
+                throw Error("fail to write file: " + path);
+            dz_ = true;
+            zbuf_.resize(1 << 16);
+            const uint8_t head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255};  // RFC 1952: no flags, no time, OS unknown
+            put_plain(head, sizeof head);
+        } else if (compress) {
             std::string mode = "wb" + std::to_string(level < 0 ? 6 : (level > 9 ? 9 : level));
             gz_ = (path == "-") ? gzdopen(fileno(stdout), mode.c_str()) : gzopen(path.c_str(), mode.c_str());
             if (!gz_) throw Error("fail to write file: " + path);
             gzbuffer(gz_, 1 << 20);
         } else {
-            fp_ = (path == "-") ? stdout : fopen(path.c_str(), "wb");
-            if (!fp_) throw Error("fail to write file: " + path);
+            open_plain();
         }
     }
-    ~OutStream() { close(); }
+    ~OutStream() {
+        try { close(); } catch (...) {}
+    }
     OutStream(const OutStream &) = delete;
+    bool device_gzip() const { return dz_; }
     void write(const void *src, size_t n) {
         if (n == 0) return;
-        if (gz_) {
+        if (dz_) {
+            size_t done = 0;
+            while (done < n) {
+                const uInt chunk = (uInt)std::min<size_t>(n - done, 1u << 30);
+                crc_ = crc32(crc_, (const Bytef *)src + done, chunk);
+                z_.next_in = (Bytef *)const_cast<void *>(src) + done;
+                z_.avail_in = chunk;
+                run_deflate(Z_NO_FLUSH);
+                done += chunk;
+            }
+            raw_len_ += n;
+        } else if (gz_) {
             size_t done = 0;
             while (done < n) {
                 unsigned chunk = (unsigned)std::min<size_t>(n - done, 1u << 30);
                 if (gzwrite(gz_, (const char *)src + done, chunk) != (int)chunk) throw Error("write error: " + path_);
                 done += chunk;
             }
-        } else if (fwrite(src, 1, n, fp_) != n) {
-            throw Error("write error: " + path_);
+        } else {
+            put_plain(src, n);
         }
     }
+    // device gzip only: `fragment` is raw_len bytes deflated elsewhere as a byte-aligned run of blocks without a final one;
+    // crc_of_raw = the CRC-32 of those raw_len bytes alone
+    void write_deflated(const void *fragment, size_t n, uint32_t crc_of_raw, uint64_t raw_len) {
+        if (!dz_) throw Error("write error: " + path_);
+        z_.next_in = nullptr;
+        z_.avail_in = 0;
+        run_deflate(Z_SYNC_FLUSH);  // ends on a byte boundary
+        put_plain(fragment, n);
+        static_assert(sizeof(z_off_t) == 8, "bodies are longer than 2 GiB");
+        crc_ = (uint32_t)crc32_combine(crc_, crc_of_raw, (z_off_t)raw_len);
+        raw_len_ += raw_len;
+    }
     void close() {
+        if (dz_) {
+            dz_ = false;
+            z_.next_in = nullptr;
+            z_.avail_in = 0;
+            run_deflate(Z_FINISH);
+            deflateEnd(&z_);
+            uint8_t tail[8];
+            for (int i = 0; i < 4; i++) {
+                tail[i] = (uint8_t)(crc_ >> (8 * i));
+                tail[4 + i] = (uint8_t)(raw_len_ >> (8 * i));
+            }
+            put_plain(tail, sizeof tail);
+        }
         if (gz_) { gzclose(gz_); gz_ = nullptr; }
         if (fp_) { if (fp_ != stdout) fclose(fp_); else fflush(fp_); fp_ = nullptr; }
     }
 
   private:
+    void open_plain() {
+        fp_ = (path_ == "-") ? stdout : fopen(path_.c_str(), "wb");
+        if (!fp_) throw Error("fail to write file: " + path_);
+    }
+    void put_plain(const void *src, size_t n) {
+        if (n && fwrite(src, 1, n, fp_) != n) throw Error("write error: " + path_);
+    }
+    // everything zlib will give for the input at hand, to the file
+    void run_deflate(int flush) {
+        for (;;) {
+            z_.next_out = zbuf_.data();
+            z_.avail_out = (uInt)zbuf_.size();
+            const int rc = deflate(&z_, flush);
+            if (rc == Z_STREAM_ERROR) throw Error("write error: " + path_);
+            put_plain(zbuf_.data(), zbuf_.size() - z_.avail_out);
+            if (z_.avail_out != 0) break;  // (Z_BUF_ERROR: nothing was pending, e.g. a second flush in a row)
+        }
+    }
     std::string path_;
     gzFile gz_ = nullptr;
     FILE *fp_ = nullptr;
+    bool dz_ = false;
+    z_stream z_;
+    std::vector<uint8_t> zbuf_;
+    uint32_t crc_ = 0;
+    uint64_t raw_len_ = 0;
 };
 
 static inline void put_be(uint8_t *p, uint64_t v, int n) {
@@ -351,6 +426,13 @@ class Writer {
     void write_body(const uint8_t *body, size_t n) {
         write_header();
         out_.write(body, n);
+    }
+
+    // the same for a stream in device-gzip mode: the body arrives deflated (OutStream::write_deflated)
+    bool device_gzip() const { return out_.device_gzip(); }
+    void write_body_deflated(const uint8_t *fragment, size_t n, uint32_t crc_of_body, uint64_t body_len) {
+        write_header();
+        out_.write_deflated(fragment, n, crc_of_body, body_len);
     }
 
     void flush() {

@@ -47,6 +47,7 @@ SYMBOLS = [
     "ukm_taxonomy_set_ranks", "ukm_rank_filter_plan", "ukm_rank_pass", "ukm_rfilter", "ukm_tsplit",
     "ukm_unik_decode", "ukm_unik_encode", "ukm_unik_encode_bound",
     "ukm_view", "ukm_view_bound", "ukm_dump",
+    "ukm_deflate", "ukm_deflate_bound", "ukm_crc32_combine",
 ]
 
 
@@ -193,6 +194,11 @@ def load():
     L.ukm_view_bound.argtypes = [u64, i32, i32, u32]
     L.ukm_view_bound.restype = u64
     L.ukm_dump.argtypes = [vp, vp, u64, i32, u32, vp, vp, u64, pu64, pu64]
+    L.ukm_deflate.argtypes = [vp, vp, u64, u32, vp, u64, pu64, C.POINTER(u32)]
+    L.ukm_deflate_bound.argtypes = [u64, u32]
+    L.ukm_deflate_bound.restype = u64
+    L.ukm_crc32_combine.argtypes = [u32, u32, u64]
+    L.ukm_crc32_combine.restype = u32
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
     L.ukm_max_hash.argtypes = [u64]
     L.ukm_max_hash.restype = u64
@@ -291,6 +297,19 @@ def unik_encode_bound(n, k, flags, taxid_bytes=0):
 def view_bound(n, k, hashed=False, fmt=VIEW_KMER):
     """bytes the text of n records takes at most (exact for VIEW_KMER of codes that are not hashed); pure host code"""
     return int(load().ukm_view_bound(int(n), int(k), int(bool(hashed)), int(fmt)))
+
+
+DEFLATE_FINAL, DEFLATE_GZIP = 1, 2   # include/unikmer_hip.h: UKM_DEFLATE_*
+
+
+def deflate_bound(n_bytes, final=False, gzip=False):
+    """bytes Context.deflate writes at most for n_bytes of input; pure host code"""
+    return int(load().ukm_deflate_bound(int(n_bytes), (DEFLATE_FINAL if final else 0) | (DEFLATE_GZIP if gzip else 0)))
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """the CRC-32 of A followed by B from zlib.crc32(A), zlib.crc32(B) and len(B); pure host code"""
+    return int(load().ukm_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
 
 
 class Context:
@@ -695,6 +714,20 @@ class Context:
         m = C.c_uint64()
         _check(self.L.ukm_unik_encode(self.h, pk, pt, n, int(k), int(flags), int(taxid_bytes), po, cap if n else 0, C.byref(m)), m.value)
         return out[: m.value]
+
+    # ---- deflate (the gzip writer behind a .unik body) ----
+    def deflate(self, data, crc=0, final=False, gzip=False, out=None):
+        """(fragment, crc): `data` (uint8) as a byte-aligned run of deflate blocks, Huffman coding only, where the input lives;
+        crc in: zlib.crc32 of what precedes data in the caller's stream, out: of that followed by data.  final: the fragment
+        ends the deflate stream; gzip: it is a complete gzip member.  Without `out` it is sized by deflate_bound."""
+        pd, n, k1 = _ptr(data, np.uint8)
+        flags = (DEFLATE_FINAL if final else 0) | (DEFLATE_GZIP if gzip else 0)
+        m, c = C.c_uint64(), C.c_uint32(int(crc) & 0xFFFFFFFF)
+        if out is None:
+            out = _empty_like_kind(data, deflate_bound(n, final, gzip), np.uint8)
+        po, cap, _ = _ptr(out, np.uint8)
+        _check(self.L.ukm_deflate(self.h, pd, n, flags, po, cap, C.byref(m), C.byref(c)), m.value)
+        return out[: m.value], int(c.value)
 
     # ---- k-mer text (`unikmer view` / `unikmer dump`) ----
     def view(self, keys, taxids=None, file_taxid=0, *, k, hashed=False, fmt=VIEW_KMER, out=None):

@@ -1,5 +1,6 @@
 """`.unik` files for the Python user: the header is read and written here, the body goes through the device codec
-(Context.unik_decode / unik_encode).  gzip inflate and deflate are the `gzip` module's: one host thread.
+(Context.unik_decode / unik_encode).  gzip inflate is the `gzip` module's, one host thread, and so is deflate unless
+save() is told deflate="device" (Context.deflate).
 
 The header layout is the one unikmer_amd/host/unik.hpp states (unik::Reader::read_header, unik::Writer::write_header),
 big-endian throughout:
@@ -8,6 +9,7 @@ big-endian throughout:
 """
 import gzip
 import struct
+import zlib
 
 import numpy as np
 
@@ -77,15 +79,36 @@ def load(ctx, path, device=True, ignore_taxid=False):
     return h, keys, taxids
 
 
-def save(ctx, path, header, keys, taxids=None, compress=True):
+GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255])
+
+
+def save(ctx, path, header, keys, taxids=None, compress=True, deflate="host"):
     """writes header and records; header["flag"] decides the layout (SORTED: keys must ascend pair by pair).  `number` is
-    set to the record count."""
+    set to the record count.  deflate="device" (with compress): the body is deflated where it was encoded
+    (Context.deflate: Huffman coding in independent chunks) and only the compressed bytes come to the host; the file is one
+    gzip member that inflates to the same bytes."""
+    if deflate not in ("host", "device"):
+        raise ValueError("deflate must be 'host' or 'device'")
     h = dict(header)
     n = int(keys.numel()) if lib._is_torch(keys) else len(keys)
     h["number"] = n
     if taxids is None:
         h["flag"] &= ~INCLUDE_TAXID
     body = ctx.unik_encode(keys, h["k"], h["flag"], taxids=taxids, taxid_bytes=h.get("taxid_bytes", 4))
+    if compress and deflate == "device":
+        hb = header_bytes(h)
+        z = zlib.compressobj(6, zlib.DEFLATED, -15)
+        head = z.compress(hb) + z.flush(zlib.Z_SYNC_FLUSH)   # ends on a byte boundary, no final block
+        frag, crc = ctx.deflate(body, crc=zlib.crc32(hb), final=True)
+        nbody = int(body.numel()) if lib._is_torch(body) else len(body)
+        if lib._is_torch(frag):
+            frag = frag.cpu().numpy()
+        with open(path, "wb") as f:
+            f.write(GZIP_HEADER)
+            f.write(head)
+            f.write(frag.tobytes())
+            f.write(struct.pack("<II", crc, (len(hb) + nbody) & 0xFFFFFFFF))
+        return
     if lib._is_torch(body):
         body = body.cpu().numpy()
     with (gzip.open(path, "wb", compresslevel=6) if compress else open(path, "wb")) as f:
