@@ -1,9 +1,9 @@
 // Stand-alone check of the driver's device-free layer (unikmer_amd/host/base.hpp, seqtext.hpp), built by
 // tests/test_host_units_cpu.py with -fsanitize=address,undefined: the flag parser, byte sizes, the FASTA/Q parser (plain
-// and gzipped, across its 1 MiB read boundaries), the k-mer text codec, degenerate bases, the rank-order file and the
-// nodes.dmp line parser.  Expected values are worked out by hand from the rules the code's comments state; the k-mer
-// codes were checked once against `unikmer encode -a` / `decode -a`.  The program sets the worker flag, so die() throws
-// and the messages can be compared.  usage: host_units <scratch directory>
+// and gzipped, across its 1 MiB read boundaries), the k-mer text codec, degenerate bases, the rank-order file, the
+// nodes.dmp line parser and the two-call idiom.  Expected values are worked out by hand from the rules the code's comments
+// state; the k-mer codes were checked once against `unikmer encode -a` / `decode -a`.  The program sets the worker flag, so
+// die() throws and the messages can be compared.  usage: host_units <scratch directory>
 #include <cstdio>
 #include <functional>
 
@@ -238,6 +238,32 @@ static void test_small_parsers() {
     CHECK(base_of("a/b/c.unik") == "c.unik" && base_of("c") == "c" && base_of("a/") == "");
     CHECK(out_name("-") == "-" && out_name("x") == "x.unik" && out_name("x.unik") == "x.unik" && chunk_file_name("d", 7) == "d/chunk_007.unik");
 }
+// call_grow / call_sized against a fake entry point that needs `need` entries: -7 stands for UKM_ERR_CAPACITY
+static void test_two_call_idiom() {
+    const int CAP = -7;
+    vector<u64> caps;  // the capacity of every call made
+    u64 n = 0;
+    auto fake = [&](u64 need, int other) {
+        return [&caps, need, other](u64 cap, u64 *m) { caps.push_back(cap); *m = need; return other ? other : cap < need ? -7 : 0; };
+    };
+    CHECK(call_grow(CAP, 16, &n, fake(16, 0)) == 0 && caps == (vector<u64>{16}) && n == 16);  // the first capacity fits: one call
+    caps.clear();
+    CHECK(call_grow(CAP, 16, &n, fake(40, 0)) == 0 && caps == (vector<u64>{16, 40}) && n == 40);  // ... does not: again, at the reported count
+    caps.clear();
+    CHECK(call_sized(CAP, &n, fake(5, 0)) == 0 && caps == (vector<u64>{0, 5}) && n == 5);  // the size query
+    caps.clear();
+    CHECK(call_sized(CAP, &n, fake(0, 0)) == 0 && caps == (vector<u64>{0}) && n == 0);  // ... that finds nothing to leave: not repeated
+    caps.clear();
+    u64 grows = 0;  // a call that asks for more every time: the second UKM_ERR_CAPACITY is the result, there is no third call
+    CHECK(call_grow(CAP, 1, &n, [&](u64 cap, u64 *m) { caps.push_back(cap); *m = cap + 10; grows++; return -7; }) == CAP && grows == 2);
+    CHECK(caps == (vector<u64>{1, 11}) && n == 21);
+    caps.clear();
+    CHECK(call_grow(CAP, 16, &n, fake(40, -4)) == -4 && caps == (vector<u64>{16}));  // any other code: returned at once
+    caps.clear();
+    int calls = 0;  // ... and from the second call as well
+    CHECK(call_grow(CAP, 16, &n, [&](u64 cap, u64 *m) { caps.push_back(cap); *m = 40; return calls++ ? -10 : -7; }) == -10);
+    CHECK(caps == (vector<u64>{16, 40}));
+}
 
 int main(int argc, char **argv) {
     if (argc != 2) return 2;
@@ -251,6 +277,7 @@ int main(int argc, char **argv) {
         test_extend_degenerate();
         test_rank_order(dir);
         test_small_parsers();
+        test_two_call_idiom();
     } catch (const std::exception &e) {
         fprintf(stderr, "unexpected exception: %s\n", e.what());
         return 1;

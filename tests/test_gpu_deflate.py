@@ -202,6 +202,32 @@ def test_same_call_twice_same_bytes(ctx):
     assert host(a).tobytes() == host(b).tobytes() and ca == cb
 
 
+@pytest.mark.parametrize("n", [1, CH + 1, (SCAN_WIDTH + 1) * CH + 3])
+def test_calls_do_not_depend_on_what_the_workspace_held(ctx, lib, n):
+    """sums, offsets, the scan's total, code lengths and CRCs all live in the workspace: one chunk, two, and more chunks than
+    one round of the scan workgroup, over a workspace of zeros and of ones; host input, so the source is staged there too"""
+    rng = np.random.default_rng(n)
+    data = np.minimum(rng.integers(0, 256, n, dtype=np.uint8), rng.integers(0, 256, n, dtype=np.uint8)) >> 2
+
+    def run():
+        got = []
+        for gz in (False, True):
+            frag, crc = ctx.deflate(data, gzip=gz)
+            with pytest.raises(lib.CapacityError) as e:  # the size query
+                ctx.deflate(data, gzip=gz, out=np.empty(0, dtype=np.uint8))
+            got.append((frag.tobytes(), len(frag), crc, e.value.needed))
+        return got
+    want = run()
+    assert all(size == needed and crc == zlib.crc32(data.tobytes()) for _, size, crc, needed in want)
+    assert gzip.decompress(want[1][0]) == data.tobytes()
+    for byte in (0x00, 0xFF):
+        ctx.set_option("ws_poison", byte)
+        try:
+            assert run() == want
+        finally:
+            ctx.set_option("ws_poison", None)
+
+
 def test_empty_input(ctx, lib):
     e = np.empty(0, dtype=np.uint8)
     for arr in (e, dev(e)):

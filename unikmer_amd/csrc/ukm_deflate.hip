@@ -4,13 +4,13 @@
 // The source is cut into chunks of DFL_CHUNK bytes.  A chunk becomes ONE dynamic block of literals and end-of-block followed
 // by an empty stored block (the sync-flush marker 00 00 FF FF, which restores byte alignment) -- or, where that would not be
 // smaller, one stored block of the chunk's bytes: 5 bytes more than the input and never worse.  Chunks start and end on byte
-// boundaries, so their outputs concatenate.  Reduce-then-scan, the plan of ukm_unik.hip's sorted encoder, no look-back:
+// boundaries, so their outputs concatenate.  Size-then-write (ukm_bytes.h: SizeScan), no look-back:
 //   1. dfl_sum_kernel, a workgroup per chunk: the chunk to LDS as aligned 16-byte words (load_image), a histogram in LDS
 //      with a private copy per wave, the chunk's raw CRC-32 from per-thread slices, the used symbols ranked by (frequency,
 //      symbol) by all threads, then ONE lane merges the Huffman tree, limits the lengths (ukm_huff.h) and sizes the block
 //      header; the chunk's output size, its 257 code lengths, its stored-or-dynamic choice and its raw CRC go to the workspace.
-//   2. scan_sums_kernel (ukm_bytes.h): one workgroup, output offsets and the total.  The total is read back: the size query
-//      and a capacity failure end here.  The chunks' CRCs are read back and combined on the host.
+//   2. the protocol's scan and capacity step: the size query and a capacity failure end here.  Behind them the chunks' CRCs
+//      are read back and combined on the host.
 //   3. dfl_write_kernel, a workgroup per chunk: canonical codes from the stored lengths, one lane writes the block header into
 //      a zeroed LDS image that starts at the output's address mod 16, every thread sizes its slice, a workgroup scan gives
 //      bit offsets, the codes are OR-ed into the image 32 bits at a time, flush_image writes whole aligned words with a head
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(NT) void dfl_sum_kernel(const u8 *src, u64 n_bytes,
     __shared__ H::HeaderScratch s_hs;
     __shared__ u32 s_hist[DFL_WAVES * H::LIT_SYMS];
     __shared__ u32 s_freq[H::LIT_SYMS];
-    __shared__ u32 s_tab[256], s_pow[16], s_scan[NT];
+    __shared__ u32 s_tab[256], s_pow[16], s_scan[SCAN_LDS];
     __shared__ u32 s_len32[DFL_META / 4];
     __shared__ u32 s_crc, s_used, s_hdr_bits;
     u8 *s_len = (u8 *)s_len32;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(NT) void dfl_sum_kernel(const u8 *src, u64 n_bytes,
     }
     __syncthreads();
     u32 literal_bits;
-    (void)block_excl_scan(s_freq[tid] * (u32)s_len[tid], s_scan, tid, &literal_bits);
+    (void)block_excl_scan_u32<NT>(s_freq[tid] * (u32)s_len[tid], s_scan, &literal_bits);
     if (tid == 0) {
         const u32 dynamic = H::dynamic_bytes(s_hdr_bits, literal_bits, s_len[H::EOB]), stored = len + (u32)DFL_STORED;
         const bool keep = dynamic < stored;
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(NT) void dfl_write_kernel(const u8 *src, u64 n_byte
     __shared__ H::HeaderScratch s_hs;
     __shared__ u32 s_code[H::LIT_SYMS];  // code | length << 16
     __shared__ u32 s_len32[DFL_META / 4];
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     __shared__ u32 s_count[16], s_first[16];
     __shared__ u32 s_hdr_end;
     const u8 *s_len = (const u8 *)s_len32;
@@ -157,7 +157,8 @@ __global__ __launch_bounds__(NT) void dfl_write_kernel(const u8 *src, u64 n_byte
     const u32 len = chunk_len(n_bytes, chunk);
     const u32 nbytes = sums[chunk];
     u8 *dst = out + offs[chunk];
-    const int shift = (int)((uintptr_t)dst & 15);
+    int shift;
+    u8 *O = image_at(dst, s_out, &shift);
     const int shift_in = load_image(src, chunk * (u64)DFL_CHUNK, len, s_in, tid);
     const u32 *m = (const u32 *)(meta + chunk * (u64)DFL_META);
     for (int i = tid; i < DFL_META / 4; i += NT) s_len32[i] = m[i];
@@ -165,7 +166,6 @@ __global__ __launch_bounds__(NT) void dfl_write_kernel(const u8 *src, u64 n_byte
     if (tid < 16) s_count[tid] = 0;
     __syncthreads();
     const u8 *B = (const u8 *)s_in + shift_in;
-    u8 *O = (u8 *)s_out + shift;
     if (s_len[H::LIT_SYMS]) {  // stored: 00 (not final, BTYPE 00, padding), LEN, NLEN, the bytes
         if (tid == 0) {
             O[0] = 0;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(NT) void dfl_write_kernel(const u8 *src, u64 n_byte
     u32 bits = 0;
     for (u32 p = lo; p < hi; p++) bits += s_code[B[p]] >> 16;
     u32 literal_bits;
-    const u32 at = block_excl_scan(bits, s_scan, tid, &literal_bits);
+    const u32 at = block_excl_scan_u32<NT>(bits, s_scan, &literal_bits);
     u32 *img = (u32 *)s_out;
     if (lo < hi) {
         const u32 pos = s_hdr_end + at;
@@ -277,26 +277,18 @@ extern "C" int ukm_deflate(ukm_ctx *ctx, const uint8_t *src, uint64_t n_bytes, u
     int rc = [&]() -> int {
         const u8 *b = nullptr;
         u8 *ob = nullptr, *meta = nullptr;
-        u32 *sums = nullptr, *crcs = nullptr;
-        u64 *offs = nullptr, *ctl = nullptr;
-        u64 body = 0;
+        u32 *crcs = nullptr;
+        SizeScan z;  // of the chunks: z.total stays 0 without one
         if (nchunks) {
             UKM_TRY(ukm_in_t(ctx, src, n_bytes, &b));
-            UKM_TRY(ws_alloc_t(ctx, nchunks, &sums));
+            UKM_TRY(size_alloc(ctx, nchunks, -1, &z));
             UKM_TRY(ws_alloc_t(ctx, nchunks, &crcs));
-            UKM_TRY(ws_alloc_t(ctx, nchunks, &offs));
-            UKM_TRY(ws_alloc_t(ctx, 2, &ctl));
             UKM_TRY(ws_alloc_t(ctx, nchunks * DFL_META, &meta));
-            hipLaunchKernelGGL(dfl_sum_kernel, dim3((unsigned)nchunks), dim3(NT), 0, ctx->stream, b, n_bytes, sums, meta, crcs);
-            (void)hipEventRecord(ctx->ev_k0, ctx->stream);  // ukm_last_kernel_ms: the scan between the two passes, its read-backs included
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(NT), 0, ctx->stream, (const u32 *)sums, nchunks, offs, ctl);
-            UKM_HIP(hipGetLastError());
-            UKM_TRY(ukm_read_u64(ctx, ctl, &body, 1));
+            hipLaunchKernelGGL(dfl_sum_kernel, dim3((unsigned)nchunks), dim3(NT), 0, ctx->stream, b, n_bytes, z.sums, meta, crcs);
+            UKM_TRY(size_scan(ctx, nchunks, &z));
         }
-        const u64 need = nhead + body + ntail;
-        *n_out = need;
-        if (out_cap < need) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the fragment takes %llu bytes, out_cap is %llu", name, (unsigned long long)need,
-                                     (unsigned long long)out_cap);
+        const u64 body = z.total, need = nhead + body + ntail;
+        UKM_TRY(out_fits(name, "the fragment takes", "bytes", need, out_cap, n_out));
         u32 crc = *crc32;
         if (nchunks) {  // the register after every chunk: times x^(8 * the chunk's bytes), plus the chunk's raw CRC
             std::vector<u32> raw(nchunks);
@@ -310,10 +302,9 @@ extern "C" int ukm_deflate(ukm_ctx *ctx, const uint8_t *src, uint64_t n_bytes, u
         }
         UKM_TRY(ukm_out_t(ctx, out, need, &ob));
         if (nchunks) {
-            (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-            ctx->evk_valid = true;
+            write_begins(ctx);
             hipLaunchKernelGGL(dfl_write_kernel, dim3((unsigned)nchunks), dim3(NT), 0, ctx->stream, b, n_bytes, (const u8 *)meta,
-                               (const u64 *)offs, (const u32 *)sums, ob + nhead);
+                               (const u64 *)z.offs, (const u32 *)z.sums, ob + nhead);
         }
         if (nhead + ntail) {
             Edges e;

@@ -1,12 +1,13 @@
 // ukm_text.hip — ukm_view / ukm_dump: records to the text `unikmer view` prints, and the text `unikmer dump` reads back to
-// records.  The byte-image machinery is ukm_bytes.h's (shared with ukm_unik.hip); neither call needs a look-back.
+// records.  The byte-image machinery and the size-then-write protocol both calls follow are ukm_bytes.h's (shared with
+// ukm_unik.hip and ukm_deflate.hip); neither call needs a look-back.
 //
 // view.  The one fixed-width case (UKM_VIEW_KMER of codes that are not hashed: k + 1 bytes a line) is one kernel, a tile of
 // FIXV_RECS lines built in an LDS image and flushed as aligned 16-byte words.  Every other format has lines whose length
-// depends on the data (decimal codes of 1..20 digits, decimal taxids of 1..10), reduce-then-scan:
-//   1. view_sum_kernel: the bytes of a tile of VIEW_RECS records (digit counts from comparisons against the powers of ten),
-//   2. scan_sums_kernel: the tile offsets and the size of the whole text -- the size query and a capacity failure end here,
-//   3. view_write_kernel: scans the lengths of its records in LDS, builds the lines in the image, flushes it.
+// depends on the data (decimal codes of 1..20 digits, decimal taxids of 1..10), size-then-write (ukm_bytes.h: SizeScan):
+//   size:  view_sum_kernel, the bytes of a tile of VIEW_RECS records (digit counts from comparisons against the powers of ten),
+//   write: view_write_kernel scans the lengths of its records in LDS, builds the lines in the image, flushes it.
+// Both take a thread's records and their bytes from view_load: the offsets of the second pass are the sizes of the first.
 // The image is sized by the longest line the format can give (VIEW_RECS x 32, 64 or 121 bytes: three instantiations), so
 // the short formats do not pay the LDS of FASTQ.
 //
@@ -15,9 +16,9 @@
 // decidable -- the byte in front is an LF, or it is offset 0 -- so every thread looks at DUMP_VT consecutive positions, the
 // starts found are compacted in LDS (one scan), and thread i parses line i: a wave parses 64 lines at once, where parsing at
 // the positions themselves would run the parser once for every position a lane holds, each time for the few lanes at a start.
-//   1. dump_count_kernel: records per tile; the lowest start of a line outside the grammar by a 64-bit atomicMin,
-//   2. scan_sums_kernel,
-//   3. dump_write_kernel: parses again, ranks the tile's records in LDS (line order), stores codes and taxids.
+//   size:  dump_count_kernel, records per tile; the lowest start of a line outside the grammar by a 64-bit atomicMin into
+//          the protocol's flag word,
+//   write: dump_write_kernel parses again, ranks the tile's records in LDS (line order), stores codes and taxids.
 #include <algorithm>
 
 #include "ukm_bytes.h"
@@ -95,6 +96,20 @@ __device__ inline u32 view_len(const ViewFmt f, u64 code, u32 taxid) {
     default: return 1 + dc + (f.with_t ? 1 + dt : 0) + 1 + kl + 1 + 2 + (u32)f.k + 1;  // FASTQ
     }
 }
+// a thread's VIEW_VT records from record r0 on (zeros behind record n - 1) and the bytes of their lines
+__device__ inline u32 view_load(const u64 *keys, const u32 *tax, u32 file_taxid, u64 n, const ViewFmt f, u64 r0, u64 *code, u32 *tx) {
+    u32 bytes = 0;
+#pragma unroll
+    for (int s = 0; s < VIEW_VT; s++) {
+        code[s] = 0;
+        tx[s] = 0;
+        if (r0 + s >= n) continue;
+        code[s] = keys[r0 + s];
+        tx[s] = tax ? tax[r0 + s] : file_taxid;
+        bytes += view_len(f, code[s], tx[s]);
+    }
+    return bytes;
+}
 __device__ inline u32 put_K(u8 *B, u32 at, const ViewFmt f, u64 code, u32 dc) {
     return f.hashed ? put_dec(B, at, code, dc) : put_kmer(B, at, code, f.k);
 }
@@ -148,8 +163,8 @@ __global__ __launch_bounds__(NT) void view_fixed_kernel(const u64 *keys, u64 n, 
     const u32 m = (u32)(n - r0 < (u64)FIXV_RECS ? n - r0 : (u64)FIXV_RECS);
     const u32 R = (u32)k + 1u;
     u8 *dst = out + r0 * R;
-    const int shift = (int)((uintptr_t)dst & 15);
-    u8 *B = (u8 *)s_img + shift;
+    int shift;
+    u8 *B = image_at(dst, s_img, &shift);
     for (u32 r = (u32)tid; r < m; r += NT) {
         const u32 at = put_kmer(B, r * R, keys[r0 + r], k);
         B[at] = '\n';
@@ -159,17 +174,13 @@ __global__ __launch_bounds__(NT) void view_fixed_kernel(const u64 *keys, u64 n, 
 }
 
 __global__ __launch_bounds__(NT) void view_sum_kernel(const u64 *keys, const u32 *tax, u32 file_taxid, u64 n, ViewFmt f, u32 *sums) {
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     const int tid = (int)threadIdx.x;
-    const u64 r0 = (u64)blockIdx.x * VIEW_RECS + (u64)tid * VIEW_VT;
-    u32 bytes = 0;
-    for (int s = 0; s < VIEW_VT; s++) {
-        const u64 r = r0 + s;
-        if (r >= n) break;
-        bytes += view_len(f, keys[r], tax ? tax[r] : file_taxid);
-    }
+    u64 code[VIEW_VT];
+    u32 tx[VIEW_VT];
+    const u32 bytes = view_load(keys, tax, file_taxid, n, f, (u64)blockIdx.x * VIEW_RECS + (u64)tid * VIEW_VT, code, tx);
     u32 total;
-    (void)block_excl_scan(bytes, s_scan, tid, &total);
+    (void)block_excl_scan_u32<NT>(bytes, s_scan, &total);
     if (tid == 0) sums[blockIdx.x] = total;
 }
 
@@ -178,26 +189,20 @@ template <int LINE>
 __global__ __launch_bounds__(NT) void view_write_kernel(const u64 *keys, const u32 *tax, u32 file_taxid, u64 n, ViewFmt f, const u64 *offs,
                                                         u8 *out) {
     __shared__ uint4 s_img[(VIEW_RECS * LINE + 32) / 16];
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     const int tid = (int)threadIdx.x;
     const u64 r0 = (u64)blockIdx.x * VIEW_RECS + (u64)tid * VIEW_VT;
     u64 code[VIEW_VT];
     u32 tx[VIEW_VT];
-    u32 bytes = 0;
-#pragma unroll
-    for (int s = 0; s < VIEW_VT; s++) {
-        code[s] = 0;
-        tx[s] = 0;
-        if (r0 + s >= n) continue;
-        code[s] = keys[r0 + s];
-        tx[s] = tax ? tax[r0 + s] : file_taxid;
-        bytes += view_len(f, code[s], tx[s]);
-    }
+    const u32 bytes = view_load(keys, tax, file_taxid, n, f, r0, code, tx);
     u32 total;
-    u32 at = block_excl_scan(bytes, s_scan, tid, &total);
+    u32 at = block_excl_scan_u32<NT>(bytes, s_scan, &total);
+    // one register: left alone the compiler carries `at` as the wave scan's ten unsummed terms through view_put (88 VGPRs
+    // where 80 give six waves a SIMD)
+    asm volatile("" : "+v"(at));
     u8 *dst = out + offs[blockIdx.x];
-    const int shift = (int)((uintptr_t)dst & 15);
-    u8 *B = (u8 *)s_img + shift;
+    int shift;
+    u8 *B = image_at(dst, s_img, &shift);
 #pragma unroll
     for (int s = 0; s < VIEW_VT; s++) {
         if (r0 + s >= n) break;
@@ -318,7 +323,7 @@ __device__ inline u32 dump_starts(const u8 *B, u64 n_bytes, u64 start, unsigned 
         if (at < n_bytes && (at == 0 || B[(int)p - 1] == '\n') && B[p] != '\n') mask |= 1u << j;
     }
     u32 total;
-    u32 r = block_excl_scan((u32)__popc(mask), s_scan, tid, &total);
+    u32 r = block_excl_scan_u32<NT>((u32)__popc(mask), s_scan, &total);
     for (int j = 0; j < DUMP_VT; j++)
         if (mask & (1u << j)) s_start[r++] = (unsigned short)(tid * DUMP_VT + j);
     __syncthreads();
@@ -334,7 +339,7 @@ __device__ inline int dump_line(const u8 *B, u64 n_bytes, u64 start, u32 p, int 
 __global__ __launch_bounds__(NT) void dump_count_kernel(const u8 *text, u64 n_bytes, int k, u32 flags, u32 *sums, u64 *ctl) {
     __shared__ uint4 s_img[DUMP_IMG / 16];
     __shared__ unsigned short s_start[DUMP_LINES];
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     const int tid = (int)threadIdx.x;
     const u64 start = (u64)blockIdx.x * DUMP_TILE;
     const u8 *B = dump_load(text, n_bytes, start, s_img, tid);
@@ -351,7 +356,7 @@ __global__ __launch_bounds__(NT) void dump_count_kernel(const u8 *text, u64 n_by
         if (r == LN_BAD && bad == ~0ull) bad = start + p;
     }
     u32 total;
-    (void)block_excl_scan(cnt, s_scan, tid, &total);
+    (void)block_excl_scan_u32<NT>(cnt, s_scan, &total);
     if (tid == 0) sums[blockIdx.x] = total;
     if (bad != ~0ull) atomicMin((unsigned long long *)&ctl[1], (unsigned long long)bad);
 }
@@ -363,7 +368,7 @@ __global__ __launch_bounds__(NT) void dump_write_kernel(const u8 *text, u64 n_by
     __shared__ u32 s_tax[DUMP_LINES];
     __shared__ unsigned short s_start[DUMP_LINES];
     __shared__ u8 s_rec[DUMP_LINES];
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     const int tid = (int)threadIdx.x;
     const u64 start = (u64)blockIdx.x * DUMP_TILE;
     const u8 *B = dump_load(text, n_bytes, start, s_img, tid);
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(NT) void dump_write_kernel(const u8 *text, u64 n_by
     u32 cnt = 0;
     for (u32 i = i0; i < i0 + DUMP_LVT && i < nl; i++) cnt += s_rec[i];
     u32 total;
-    u64 o = offs[blockIdx.x] + block_excl_scan(cnt, s_scan, tid, &total);
+    u64 o = offs[blockIdx.x] + block_excl_scan_u32<NT>(cnt, s_scan, &total);
     for (u32 i = i0; i < i0 + DUMP_LVT && i < nl; i++) {
         if (!s_rec[i]) continue;
         out_keys[o] = s_code[i];
@@ -419,9 +424,7 @@ extern "C" int ukm_view(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxi
         u8 *ob = nullptr;
         if (base == UKM_VIEW_KMER && !hashed) {
             const u64 need = n * (u64)(k + 1);
-            *n_out = need;
-            if (out_cap < need) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the text takes %llu bytes, out_cap is %llu", name, (unsigned long long)need,
-                                         (unsigned long long)out_cap);
+            UKM_TRY(out_fits(name, "the text takes", "bytes", need, out_cap, n_out));
             const u64 nblocks = (n + FIXV_RECS - 1) / FIXV_RECS;
             if (nblocks > MAX_GRID) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu records in one call", name, (unsigned long long)n);
             UKM_TRY(ukm_in_t(ctx, keys, n, &dk));
@@ -440,31 +443,22 @@ extern "C" int ukm_view(ukm_ctx *ctx, const uint64_t *keys, const uint32_t *taxi
         UKM_TRY(ukm_in_t(ctx, keys, n, &dk));
         const bool uses_t = base == UKM_VIEW_KMER_TAXID || base == UKM_VIEW_TAXID || with_t;
         if (taxids && uses_t) UKM_TRY(ukm_in_t(ctx, taxids, n, &dt));
-        u32 *sums = nullptr;
-        u64 *offs = nullptr, *ctl = nullptr;
-        UKM_TRY(ws_alloc_t(ctx, ntiles, &sums));
-        UKM_TRY(ws_alloc_t(ctx, ntiles, &offs));
-        UKM_TRY(ws_alloc_t(ctx, 2, &ctl));
-        hipLaunchKernelGGL(view_sum_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, dt, file_taxid, n, f, sums);
-        (void)hipEventRecord(ctx->ev_k0, ctx->stream);  // ukm_last_kernel_ms: the scan between the two passes, its read-back included
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(NT), 0, ctx->stream, (const u32 *)sums, ntiles, offs, ctl);
-        UKM_HIP(hipGetLastError());
-        u64 need = 0;
-        UKM_TRY(ukm_read_u64(ctx, ctl, &need, 1));
-        *n_out = need;
-        if (out_cap < need) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the text takes %llu bytes, out_cap is %llu", name, (unsigned long long)need,
-                                     (unsigned long long)out_cap);
-        UKM_TRY(ukm_out_t(ctx, out_bytes, need, &ob));
-        (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-        ctx->evk_valid = true;
+        SizeScan z;
+        UKM_TRY(size_alloc(ctx, ntiles, -1, &z));
+        hipLaunchKernelGGL(view_sum_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, dt, file_taxid, n, f, z.sums);
+        UKM_TRY(size_scan(ctx, ntiles, &z));
+        UKM_TRY(out_fits(name, "the text takes", "bytes", z.total, out_cap, n_out));
+        UKM_TRY(ukm_out_t(ctx, out_bytes, z.total, &ob));
+        write_begins(ctx);
         const u32 line = view_line_max(base, with_t, k, hashed != 0);
         const dim3 grid((unsigned)ntiles), block(NT);
+        const u64 *offs = z.offs;
         if (line <= 32)
-            hipLaunchKernelGGL(view_write_kernel<32>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, (const u64 *)offs, ob);
+            hipLaunchKernelGGL(view_write_kernel<32>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, offs, ob);
         else if (line <= 64)
-            hipLaunchKernelGGL(view_write_kernel<64>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, (const u64 *)offs, ob);
+            hipLaunchKernelGGL(view_write_kernel<64>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, offs, ob);
         else
-            hipLaunchKernelGGL(view_write_kernel<VIEW_LINE_MAX>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, (const u64 *)offs, ob);
+            hipLaunchKernelGGL(view_write_kernel<VIEW_LINE_MAX>, grid, block, 0, ctx->stream, dk, dt, file_taxid, n, f, offs, ob);
         UKM_HIP(hipGetLastError());
         return UKM_OK;
     }();
@@ -489,34 +483,23 @@ extern "C" int ukm_dump(ukm_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int
         if (ntiles > MAX_GRID) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu bytes in one call", name, (unsigned long long)n_bytes);
         const u8 *b = nullptr;
         UKM_TRY(ukm_in_t(ctx, text, n_bytes, &b));
-        u32 *sums = nullptr;
-        u64 *offs = nullptr, *ctl = nullptr;
-        UKM_TRY(ws_alloc_t(ctx, ntiles, &sums));
-        UKM_TRY(ws_alloc_t(ctx, ntiles, &offs));
-        UKM_TRY(ws_alloc_t(ctx, 2, &ctl));
-        UKM_HIP(hipMemsetAsync(ctl, 0xFF, 2 * sizeof(u64), ctx->stream));  // ctl[1]: the lowest bad line start, none yet
-        hipLaunchKernelGGL(dump_count_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, k, flags, sums, ctl);
-        (void)hipEventRecord(ctx->ev_k0, ctx->stream);  // (as in ukm_view)
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(NT), 0, ctx->stream, (const u32 *)sums, ntiles, offs, ctl);
-        UKM_HIP(hipGetLastError());
-        u64 res[2] = {0, 0};
-        UKM_TRY(ukm_read_u64(ctx, ctl, res, 2));
-        if (res[1] != ~0ull) {
-            if (bad_off) *bad_off = res[1];
-            UKM_FAIL(UKM_ERR_FORMAT, "%s: the line at byte %llu is not %s", name, (unsigned long long)res[1],
+        SizeScan z;
+        UKM_TRY(size_alloc(ctx, ntiles, 0xFF, &z));  // the flag: the lowest bad line start, none yet
+        hipLaunchKernelGGL(dump_count_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, k, flags, z.sums, z.ctl);
+        UKM_TRY(size_scan(ctx, ntiles, &z));
+        if (z.flag != ~0ull) {
+            if (bad_off) *bad_off = z.flag;
+            UKM_FAIL(UKM_ERR_FORMAT, "%s: the line at byte %llu is not %s", name, (unsigned long long)z.flag,
                      (flags & UKM_DUMP_TAXID) ? "a code, a TAB and a taxid" : "a code");
         }
-        *n_out = res[0];
-        if (out_cap < res[0]) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the text holds %llu records, out_cap is %llu", name,
-                                       (unsigned long long)res[0], (unsigned long long)out_cap);
-        if (res[0] == 0) return UKM_OK;
+        UKM_TRY(out_fits(name, "the text holds", "records", z.total, out_cap, n_out));
+        if (z.total == 0) return UKM_OK;
         u64 *ok = nullptr;
         u32 *ot = nullptr;
-        UKM_TRY(ukm_out_t(ctx, out_keys, res[0], &ok));
-        if (out_taxids) UKM_TRY(ukm_out_t(ctx, out_taxids, res[0], &ot));
-        (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-        ctx->evk_valid = true;
-        hipLaunchKernelGGL(dump_write_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, k, flags, (const u64 *)offs, ok, ot);
+        UKM_TRY(ukm_out_t(ctx, out_keys, z.total, &ok));
+        if (out_taxids) UKM_TRY(ukm_out_t(ctx, out_taxids, z.total, &ot));
+        write_begins(ctx);
+        hipLaunchKernelGGL(dump_write_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, k, flags, (const u64 *)z.offs, ok, ot);
         UKM_HIP(hipGetLastError());
         return UKM_OK;
     }();

@@ -22,10 +22,11 @@
 //      code index and prev, all threads write codes and taxids, record i by thread i.
 // No look-back: a carried prev needs all 64 bits, and a map is no sum.  Chains are never assumed to merge.
 //
-// Sorted layout, encode: reduce-then-scan as well.  enc_sum_kernel adds the byte lengths of ENC_PAIRS pairs per tile (and
-// checks the order where the Writer does), scan_sums_kernel scans the tile sums in one workgroup, enc_write_kernel builds
-// a tile's bytes in LDS and writes them as aligned 16-byte words with a head and a tail of single bytes.
-// load_image / flush_image / scan_sums_kernel and the byte helpers: ukm_bytes.h (shared with ukm_text.hip).
+// Sorted layout, encode: size-then-write (ukm_bytes.h: SizeScan).  enc_sum_kernel adds the byte lengths of ENC_PAIRS pairs
+// per tile (and raises the flag word where the Writer refuses the order), enc_write_kernel builds a tile's bytes in LDS and
+// writes them as aligned 16-byte words with a head and a tail of single bytes.  Both take a thread's deltas and their bytes
+// from enc_load.  The decode's capacity step and bracket are the protocol's too; its chain is its own.
+// load_image / flush_image / image_at, the byte helpers and the protocol: ukm_bytes.h (shared with ukm_text.hip, ukm_deflate.hip).
 #include <algorithm>
 
 #include "ukm_bytes.h"
@@ -286,8 +287,8 @@ __global__ __launch_bounds__(NT) void fixed_encode_kernel(const u64 *keys, const
     const u32 m = (u32)(n - r0 < (u64)FIX_RECS ? n - r0 : (u64)FIX_RECS);
     const u32 R = (u32)(cb + tb);
     u8 *dst = out + r0 * R;
-    const int shift = (int)((uintptr_t)dst & 15);
-    u8 *B = (u8 *)s_img + shift;
+    int shift;
+    u8 *B = image_at(dst, s_img, &shift);
     for (u32 r = (u32)tid; r < m; r += NT) {
         put_be(B + r * R, keys[r0 + r], cb);
         if (tb) put_be(B + r * R + cb, tax ? tax[r0 + r] : 0u, tb);
@@ -304,43 +305,45 @@ __device__ inline bool pair_deltas(const u64 *keys, u64 j, u64 *d0, u64 *d1) {
     return c0 < prev || c1 < c0;
 }
 
-__global__ __launch_bounds__(NT) void enc_sum_kernel(const u64 *keys, u64 npairs, int tb, u32 *sums, u64 *ctl) {
-    __shared__ u32 s_scan[NT];
-    const int tid = (int)threadIdx.x;
-    const u64 j0 = (u64)blockIdx.x * ENC_PAIRS + (u64)tid * ENC_VT;
+// a thread's ENC_VT pairs from pair j0 on: their deltas (zeros behind pair npairs - 1), the bytes of their records, and
+// *bad: the Writer refuses one of them
+__device__ inline u32 enc_load(const u64 *keys, u64 npairs, int tb, u64 j0, u64 *d0, u64 *d1, bool *bad) {
     u32 bytes = 0;
-    bool bad = false;
+    *bad = false;
     for (int s = 0; s < ENC_VT; s++) {
-        const u64 j = j0 + s;
-        if (j >= npairs) break;
-        u64 d0, d1;
-        bad |= pair_deltas(keys, j, &d0, &d1);
-        bytes += 1u + (u32)byte_len(d0) + (u32)byte_len(d1) + 2u * (u32)tb;
+        d0[s] = d1[s] = 0;
+        if (j0 + s >= npairs) continue;
+        *bad |= pair_deltas(keys, j0 + s, &d0[s], &d1[s]);
+        bytes += 1u + (u32)byte_len(d0[s]) + (u32)byte_len(d1[s]) + 2u * (u32)tb;
     }
+    return bytes;
+}
+
+__global__ __launch_bounds__(NT) void enc_sum_kernel(const u64 *keys, u64 npairs, int tb, u32 *sums, u64 *ctl) {
+    __shared__ u32 s_scan[SCAN_LDS];
+    const int tid = (int)threadIdx.x;
+    u64 d0[ENC_VT], d1[ENC_VT];
+    bool bad;
+    const u32 bytes = enc_load(keys, npairs, tb, (u64)blockIdx.x * ENC_PAIRS + (u64)tid * ENC_VT, d0, d1, &bad);
     u32 total;
-    (void)block_excl_scan(bytes, s_scan, tid, &total);
+    (void)block_excl_scan_u32<NT>(bytes, s_scan, &total);
     if (tid == 0) sums[blockIdx.x] = total;
     if (bad) atomicOr((unsigned long long *)&ctl[1], 1ull);
 }
 
 __global__ __launch_bounds__(NT) void enc_write_kernel(const u64 *keys, const u32 *tax, u64 npairs, int tb, const u64 *offs, u8 *out) {
     __shared__ uint4 s_img[ENC_IMG / 16];
-    __shared__ u32 s_scan[NT];
+    __shared__ u32 s_scan[SCAN_LDS];
     const int tid = (int)threadIdx.x;
     const u64 j0 = (u64)blockIdx.x * ENC_PAIRS + (u64)tid * ENC_VT;
     u64 d0[ENC_VT], d1[ENC_VT];
-    u32 bytes = 0;
-    for (int s = 0; s < ENC_VT; s++) {
-        d0[s] = d1[s] = 0;
-        if (j0 + s >= npairs) continue;
-        (void)pair_deltas(keys, j0 + s, &d0[s], &d1[s]);
-        bytes += 1u + (u32)byte_len(d0[s]) + (u32)byte_len(d1[s]) + 2u * (u32)tb;
-    }
+    bool bad;  // (the size pass has reported it: this launch does not happen then)
+    const u32 bytes = enc_load(keys, npairs, tb, j0, d0, d1, &bad);
     u32 total;
-    u32 at = block_excl_scan(bytes, s_scan, tid, &total);
+    u32 at = block_excl_scan_u32<NT>(bytes, s_scan, &total);
     u8 *dst = out + offs[blockIdx.x];
-    const int shift = (int)((uintptr_t)dst & 15);
-    u8 *B = (u8 *)s_img + shift;
+    int shift;
+    u8 *B = image_at(dst, s_img, &shift);
     for (int s = 0; s < ENC_VT; s++) {
         const u64 j = j0 + s;
         if (j >= npairs) break;
@@ -414,9 +417,7 @@ extern "C" int ukm_unik_decode(ukm_ctx *ctx, const uint8_t *body, uint64_t n_byt
             const u64 R = (u64)(cb + tb), n = n_bytes / R, rest = n_bytes % R;
             if (rest) UKM_FAIL(UKM_ERR_FORMAT, "%s: %s: the last record holds %llu of %llu bytes", name,
                                rest < (u64)cb ? "truncated record" : "unexpected EOF", (unsigned long long)rest, (unsigned long long)R);
-            *n_out = n;
-            if (out_cap < n) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the body holds %llu records, out_cap is %llu", name, (unsigned long long)n,
-                                      (unsigned long long)out_cap);
+            UKM_TRY(out_fits(name, "the body holds", "records", n, out_cap, n_out));
             const u64 nblocks = (n + FIX_RECS - 1) / FIX_RECS;
             if (nblocks > MAX_GRID) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu records in one call", name, (unsigned long long)n);
             UKM_TRY(ukm_in_t(ctx, body, n_bytes, &b));
@@ -437,7 +438,7 @@ extern "C" int ukm_unik_decode(ukm_ctx *ctx, const uint8_t *body, uint64_t n_byt
         UKM_TRY(ws_alloc_t(ctx, ngroups, &gstates));
         UKM_TRY(ws_alloc_t(ctx, 2, &result));
         hipLaunchKernelGGL(summary_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, tb, maps);
-        (void)hipEventRecord(ctx->ev_k0, ctx->stream);  // ukm_last_kernel_ms: the scan between the two passes, its read-back included
+        scan_begins(ctx);  // (the protocol's bracket around a scan of its own: a map is no sum)
         hipLaunchKernelGGL(group_map_kernel, dim3((unsigned)ngroups), dim3(NT), 0, ctx->stream, (const TileMap *)maps, ntiles, gmaps);
         hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(NT), 0, ctx->stream, (const TileMap *)gmaps, ngroups, ngroups,
                            (const WalkState *)nullptr, gstates, result);
@@ -446,17 +447,14 @@ extern "C" int ukm_unik_decode(ukm_ctx *ctx, const uint8_t *body, uint64_t n_byt
         UKM_TRY(ukm_read_u64(ctx, result, res, 2));
         if (res[1]) UKM_FAIL(UKM_ERR_FORMAT, "%s: unexpected EOF: the last record runs past the body's %llu bytes", name,
                              (unsigned long long)n_bytes);
-        *n_out = res[0];
-        if (out_cap < res[0]) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the body holds %llu records, out_cap is %llu", name,
-                                       (unsigned long long)res[0], (unsigned long long)out_cap);
+        UKM_TRY(out_fits(name, "the body holds", "records", res[0], out_cap, n_out));
         if (res[0] == 0) return UKM_OK;
         UKM_TRY(ws_alloc_t(ctx, ntiles, &tstates));
         UKM_TRY(ukm_out_t(ctx, out_keys, res[0], &ok));
         if (tb) UKM_TRY(ukm_out_t(ctx, out_taxids, res[0], &ot));
         hipLaunchKernelGGL(chain_kernel, dim3((unsigned)ngroups), dim3(NT), 0, ctx->stream, (const TileMap *)maps, (u64)SCAN_GROUP, ntiles,
                            (const WalkState *)gstates, tstates, (u64 *)nullptr);
-        (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-        ctx->evk_valid = true;
+        write_begins(ctx);
         hipLaunchKernelGGL(decode_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, b, n_bytes, tb, (const WalkState *)tstates, ok, ot);
         UKM_HIP(hipGetLastError());
         return UKM_OK;
@@ -480,9 +478,7 @@ extern "C" int ukm_unik_encode(ukm_ctx *ctx, const uint64_t *keys, const uint32_
         u8 *ob = nullptr;
         if (cb) {
             const u64 R = (u64)(cb + tb), need = n * R;
-            *n_out = need;
-            if (out_cap < need) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the body takes %llu bytes, out_cap is %llu", name, (unsigned long long)need,
-                                         (unsigned long long)out_cap);
+            UKM_TRY(out_fits(name, "the body takes", "bytes", need, out_cap, n_out));
             const u64 nblocks = (n + FIX_RECS - 1) / FIX_RECS;
             if (nblocks > MAX_GRID) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu records in one call", name, (unsigned long long)n);
             UKM_TRY(ukm_in_t(ctx, keys, n, &dk));
@@ -496,36 +492,21 @@ extern "C" int ukm_unik_encode(ukm_ctx *ctx, const uint64_t *keys, const uint32_
         if (ntiles > MAX_GRID) UKM_FAIL(UKM_ERR_INVALID, "%s: %llu records in one call", name, (unsigned long long)n);
         UKM_TRY(ukm_in_t(ctx, keys, n, &dk));
         if (tb) UKM_TRY(ukm_in_t(ctx, taxids, n, &dt));
-        u64 pair_bytes = 0;
-        u64 *offs = nullptr;
+        SizeScan z;  // of the pairs: z.total stays 0 without one
         if (npairs) {
-            u32 *sums = nullptr;
-            u64 *ctl = nullptr;
-            UKM_TRY(ws_alloc_t(ctx, ntiles, &sums));
-            UKM_TRY(ws_alloc_t(ctx, ntiles, &offs));
-            UKM_TRY(ws_alloc_t(ctx, 2, &ctl));
-            UKM_HIP(hipMemsetAsync(ctl, 0, 2 * sizeof(u64), ctx->stream));
-            hipLaunchKernelGGL(enc_sum_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, npairs, tb, sums, ctl);
-            (void)hipEventRecord(ctx->ev_k0, ctx->stream);  // (as in the decode: the scan and its read-back)
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(NT), 0, ctx->stream, (const u32 *)sums, ntiles, offs, ctl);
-            UKM_HIP(hipGetLastError());
-            u64 res[2] = {0, 0};
-            UKM_TRY(ukm_read_u64(ctx, ctl, res, 2));
-            if (res[1]) UKM_FAIL(UKM_ERR_UNSORTED, "%s: codes written to a sorted .unik must be ascending", name);
-            pair_bytes = res[0];
+            UKM_TRY(size_alloc(ctx, ntiles, 0, &z));  // the flag: a pair out of order
+            hipLaunchKernelGGL(enc_sum_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, npairs, tb, z.sums, z.ctl);
+            UKM_TRY(size_scan(ctx, ntiles, &z));
+            if (z.flag) UKM_FAIL(UKM_ERR_UNSORTED, "%s: codes written to a sorted .unik must be ascending", name);
         }
-        const u64 need = pair_bytes + (n & 1) * (u64)(9 + tb);
-        *n_out = need;
-        if (out_cap < need) UKM_FAIL(UKM_ERR_CAPACITY, "%s: the body takes %llu bytes, out_cap is %llu", name, (unsigned long long)need,
-                                     (unsigned long long)out_cap);
+        const u64 need = z.total + (n & 1) * (u64)(9 + tb);
+        UKM_TRY(out_fits(name, "the body takes", "bytes", need, out_cap, n_out));
         UKM_TRY(ukm_out_t(ctx, out_bytes, need, &ob));
         if (npairs) {
-            (void)hipEventRecord(ctx->ev_k1, ctx->stream);
-            ctx->evk_valid = true;
+            write_begins(ctx);
+            hipLaunchKernelGGL(enc_write_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, dt, npairs, tb, (const u64 *)z.offs, ob);
         }
-        if (npairs)
-            hipLaunchKernelGGL(enc_write_kernel, dim3((unsigned)ntiles), dim3(NT), 0, ctx->stream, dk, dt, npairs, tb, (const u64 *)offs, ob);
-        if (n & 1) hipLaunchKernelGGL(enc_single_kernel, dim3(1), dim3(64), 0, ctx->stream, dk, dt, n - 1, tb, ob + pair_bytes);
+        if (n & 1) hipLaunchKernelGGL(enc_single_kernel, dim3(1), dim3(64), 0, ctx->stream, dk, dt, n - 1, tb, ob + z.total);
         UKM_HIP(hipGetLastError());
         return UKM_OK;
     }();

@@ -1,6 +1,6 @@
 // base.hpp — the driver's device-free ground layer: errors and logging, the flag parser, byte sizes, line trimming,
-// file / directory / path helpers and the two taxonomy text parsers.  Nothing here includes unikmer_hip.h: the layer
-// compiles beside unik.hpp alone (tests/host_units.cpp runs it under the sanitizers).
+// the two-call idiom of the library's capacity contract, file / directory / path helpers and the two taxonomy text parsers.
+// Nothing here includes unikmer_hip.h: the layer compiles beside unik.hpp alone (tests/host_units.cpp runs it under the sanitizers).
 #pragma once
 #include <dirent.h>
 #include <sys/stat.h>
@@ -180,6 +180,16 @@ static long long parse_byte_size(string v) {
     if (e == v.c_str() || *e) die("parsing byte size: invalid byte size: %s", v.c_str());
     return x < 0 ? 0 : (long long)(x * unit);
 }
+
+// ---- the library's two-call idiom: a call that returns cap_err (UKM_ERR_CAPACITY) has left the count it needs in *n ------
+// call(cap, n) sizes the outputs for cap entries and runs the entry point.  call_grow: at a first capacity and, ONLY where that was
+// too small, exactly once more at the reported count; the last call's code is the result, a second cap_err included.  call_sized: the
+// size query, capacity 0 first (call passes NULL outputs then); a query that succeeds has nothing to leave and is not repeated.
+template <class Call> static int call_grow(int cap_err, u64 cap, u64 *n, Call call) {
+    const int rc = call(cap, n);
+    return rc == cap_err ? call(*n, n) : rc;
+}
+template <class Call> static int call_sized(int cap_err, u64 *n, Call call) { return call_grow(cap_err, 0, n, call); }
 
 // ---- files, directories, paths --------------------------------------------------------------------
 static bool file_exists(const string &p) { struct stat st; return stat(p.c_str(), &st) == 0; }

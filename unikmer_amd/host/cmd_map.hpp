@@ -58,15 +58,11 @@ static int cmd_locate(int argc, char **argv) {  // locate.go:57-289
     Gpu g(o.gpu);
     vector<u64> oq, opos;
     vector<u32> orec;
-    u64 n = 0, cap = std::max<u64>(1u << 16, 2 * q.size());
-    for (int attempt = 0;; attempt++) {
+    u64 n = 0;
+    ck(call_grow(UKM_ERR_CAPACITY, std::max<u64>(1u << 16, 2 * q.size()), &n, [&](u64 cap, u64 *m) {
         oq.resize(cap); opos.resize(cap); orec.resize(cap);
-        const int rc = ukm_locate(g.c, gb.bases.data(), gb.off.data(), n_rec, k, circular, in.hashed, q.data(), q.size(), oq.data(),
-                                  orec.data(), opos.data(), cap, &n);
-        if (rc == UKM_ERR_CAPACITY && attempt == 0) { cap = n; continue; }
-        ck(rc);
-        break;
-    }
+        return ukm_locate(g.c, gb.bases.data(), gb.off.data(), n_rec, k, circular, in.hashed, q.data(), q.size(), oq.data(), orec.data(), opos.data(), cap, m);
+    }));
     string buf;
     for (u64 e = 0; e < n; e++) {
         const u64 r = orec[e], j = opos[e], rs = gb.off[r], len = gb.off[r + 1] - rs;
@@ -126,15 +122,12 @@ static int cmd_map(int argc, char **argv) {  // map.go:57-491 at -x 0 -X 0, line
         else for (u64 r = 0; r <= n_rec; r++) goff.push_back(r);  // one genome per record (the first pass's numbering, map.go:260-262)
         vector<u32> orec;
         vector<u64> os, oe;
-        u64 n = 0, cap = 1u << 16;
-        for (int attempt = 0;; attempt++) {
+        u64 n = 0;
+        ck(call_grow(UKM_ERR_CAPACITY, 1u << 16, &n, [&](u64 cap, u64 *m) {
             orec.resize(cap); os.resize(cap); oe.resize(cap);
-            const int rc = ukm_map(g.c, gb.bases.data(), gb.off.data(), n_rec, goff.data(), goff.size() - 1, k, in.hashed, (const u64 *)set.p, n_set,
-                                   multi, (u64)min_len, orec.data(), os.data(), oe.data(), cap, &n);
-            if (rc == UKM_ERR_CAPACITY && attempt == 0) { cap = n; continue; }
-            ck(rc);
-            break;
-        }
+            return ukm_map(g.c, gb.bases.data(), gb.off.data(), n_rec, goff.data(), goff.size() - 1, k, in.hashed, (const u64 *)set.p, n_set,
+                           multi, (u64)min_len, orec.data(), os.data(), oe.data(), cap, m);
+        }));
         for (u64 e = 0; e < n; e++) {
             const u64 r = orec[e], rs = gb.off[r];
             if (fasta) {  // map.go:385-387: >id:start+1-end, the subsequence wrapped at 60

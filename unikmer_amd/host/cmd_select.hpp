@@ -280,10 +280,11 @@ static int cmd_tsplit(int argc, char **argv) {  // tsplit.go:58-300
     {
         Gpu g(o.gpu);
         u64 groups = 0;
-        const int rc = ukm_tsplit(g.c, in.codes.data(), in.taxids.data(), n, nullptr, 0, nullptr, nullptr, 0, &groups);  // the size query
-        if (rc != UKM_ERR_CAPACITY) ck(rc);
-        gt.resize(groups); off.resize(groups + 1);
-        ck(ukm_tsplit(g.c, in.codes.data(), in.taxids.data(), n, out.data(), n, gt.data(), off.data(), groups, &groups));
+        ck(call_sized(UKM_ERR_CAPACITY, &groups, [&](u64 cap, u64 *m) {
+            if (!cap) return ukm_tsplit(g.c, in.codes.data(), in.taxids.data(), n, nullptr, 0, nullptr, nullptr, 0, m);
+            gt.resize(cap); off.resize(cap + 1);
+            return ukm_tsplit(g.c, in.codes.data(), in.taxids.data(), n, out.data(), n, gt.data(), off.data(), cap, m);
+        }));
     }
     info("%llu taxids belonging to %zu taxids loaded", (unsigned long long)n, gt.size());
     const u32 max_taxid = in.taxid_bytes >= 4 ? 0xFFFFFFFFu : ((1u << (8 * in.taxid_bytes)) - 1);  // maxUint32N: follow the readers

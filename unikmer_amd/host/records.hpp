@@ -171,21 +171,16 @@ static Loaded load_unik(const string &file, const Options &o) {
         vector<uint8_t> body;
         r.read_body(body);
         const bool tx = L.per_record();
-        u64 n = 0, cap = r.h.number == ~0ull ? 0 : std::min<u64>(r.h.number, body.size());  // (a record takes more than a byte)
-        int rc = UKM_OK;
-        for (int attempt = 0;; attempt++) {
-            L.codes.resize(cap);
-            if (tx) L.taxids.resize(cap);
-            rc = ukm_unik_decode(c, body.data(), body.size(), r.h.k, r.h.flag, r.h.taxid_bytes, cap ? L.codes.data() : nullptr,
-                                 cap && tx ? L.taxids.data() : nullptr, cap, &n);
-            if (rc == UKM_ERR_CAPACITY && attempt == 0) { cap = n; continue; }
-            break;
-        }
+        u64 n = 0, guess = r.h.number == ~0ull ? 0 : std::min<u64>(r.h.number, body.size());  // (a record takes more than a byte)
+        const int rc = call_grow(UKM_ERR_CAPACITY, guess, &n, [&](u64 cap, u64 *m) {
+            L.codes.resize(cap); if (tx) L.taxids.resize(cap);
+            return ukm_unik_decode(c, body.data(), body.size(), r.h.k, r.h.flag, r.h.taxid_bytes, cap ? L.codes.data() : nullptr,
+                                   cap && tx ? L.taxids.data() : nullptr, cap, m);
+        });
         if (rc == UKM_ERR_FORMAT)  // the Reader's own words
             throw unik::Error(string(strstr(ukm_last_error(), "truncated record") ? "truncated record: " : "unexpected EOF: ") + file);
         ck(rc);
-        L.codes.resize(n);
-        if (tx) L.taxids.resize(n);
+        L.codes.resize(n); if (tx) L.taxids.resize(n);
         if (own) ck(ukm_ctx_trim(c));
     } else {
         r.read_all(L.codes, L.per_record() ? &L.taxids : nullptr);

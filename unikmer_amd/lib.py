@@ -257,6 +257,33 @@ def _check(rc, needed=None):
     raise cls(rc, msg)
 
 
+def _sized(call, outs, alloc):
+    """The size-query form of the two-call idiom: call(outs) -> (rc, n_out) runs an entry point on the caller's outputs; outs None:
+    call(None) asks first (NULL outputs, capacity 0: UKM_ERR_CAPACITY means n_out is the size), alloc(n_out) makes them.  Returns (outs, n_out)."""
+    if outs is None:
+        rc, n = call(None)
+        if rc != ERR_CAPACITY:
+            _check(rc)
+        outs = alloc(int(n))
+    rc, n = call(outs)
+    _check(rc, n)
+    return outs, int(n)
+
+
+def _sized_records(call, ref, tax, out, out_taxids, empty):
+    """_sized for an entry point that leaves records: call(po, pot, cap) -> (rc, n_out).  The outputs are a pair: keys (`out`) and, when
+    `tax` (the records carry taxids), taxids beside them, each made where `ref` lives when not given.  empty: no input, capacity 0."""
+    def pair(keys):
+        return keys, ((_empty_like_kind(ref, _ptr(keys, np.uint64)[1], np.uint32) if out_taxids is None else out_taxids) if tax else None)
+
+    def run(o):
+        po, cap, _ = _ptr(o and o[0], np.uint64)
+        pot, ncap, _ = _ptr(o and o[1], np.uint32)
+        return call(po, pot, 0 if empty else min(cap, ncap) if tax else cap)
+    (keys, taxids), n = _sized(run, None if out is None else pair(out), lambda need: pair(_empty_like_kind(ref, need, np.uint64)))
+    return keys[:n], (taxids[:n] if tax else None)
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -667,20 +694,17 @@ class Context:
         pt, nt, k2 = _ptr(taxids, np.uint32)
         assert taxids is None or nt == n
         g = C.c_uint64()
-        if group_taxids is None or group_off is None:
-            rc = self.L.ukm_tsplit(self.h, pk, pt, n, None, 0, None, None, 0, C.byref(g))
-            if rc != ERR_CAPACITY:
-                _check(rc)
-            group_taxids = _empty_like_kind(keys, g.value, np.uint32)
-            group_off = _empty_like_kind(keys, g.value + 1, np.uint64)
-        if out is None:
-            out = _empty_like_kind(keys, n, np.uint64)
-        po, cap, _ = _ptr(out, np.uint64)
-        pg, gcap, _ = _ptr(group_taxids, np.uint32)
-        pf, fcap, _ = _ptr(group_off, np.uint64)
-        # group_off holds one entry more than group_taxids: the capacity is what both arrays take
-        _check(self.L.ukm_tsplit(self.h, pk, pt, n, po, cap if n else 0, pg, pf, min(gcap, max(fcap, 1) - 1), C.byref(g)), g.value)
-        return out[:n], group_taxids[: g.value], group_off[: g.value + 1 if n else 0]
+        out = _empty_like_kind(keys, n, np.uint64) if out is None else out
+
+        def call(groups):
+            po, cap, _ = _ptr(out if groups else None, np.uint64)
+            pg, gcap, _ = _ptr(groups and groups[0], np.uint32)
+            pf, fcap, _ = _ptr(groups and groups[1], np.uint64)
+            # group_off holds one entry more than group_taxids: the capacity is what both arrays take
+            return self.L.ukm_tsplit(self.h, pk, pt, n, po, cap if n else 0, pg, pf, min(gcap, max(fcap, 1) - 1), C.byref(g)), g.value
+        (group_taxids, group_off), ng = _sized(call, None if group_taxids is None or group_off is None else (group_taxids, group_off),
+                                               lambda m: (_empty_like_kind(keys, m, np.uint32), _empty_like_kind(keys, m + 1, np.uint64)))
+        return out[:n], group_taxids[:ng], group_off[: ng + 1 if n else 0]
 
     # ---- .unik bodies (the bytes behind a file's header, inflated; layout: host/unik.hpp) ----
     def unik_decode(self, body, k, flags, taxid_bytes=0, with_taxids=True, out=None, out_taxids=None):
@@ -689,19 +713,8 @@ class Context:
         pb, nb, k1 = _ptr(body, np.uint8)
         tax = bool(flags & UNIK_INCLUDE_TAXID) and (with_taxids or out_taxids is not None)
         n = C.c_uint64()
-        if out is None:
-            rc = self.L.ukm_unik_decode(self.h, pb, nb, int(k), int(flags), int(taxid_bytes), None, None, 0, C.byref(n))
-            if rc != ERR_CAPACITY:
-                _check(rc)
-            out = _empty_like_kind(body, n.value, np.uint64)
-        po, cap, _ = _ptr(out, np.uint64)
-        if tax and out_taxids is None:
-            out_taxids = _empty_like_kind(body, cap, np.uint32)
-        pot, ncap, _ = _ptr(out_taxids if tax else None, np.uint32)
-        if tax:
-            cap = min(cap, ncap)
-        _check(self.L.ukm_unik_decode(self.h, pb, nb, int(k), int(flags), int(taxid_bytes), po, pot, cap if nb else 0, C.byref(n)), n.value)
-        return out[: n.value], (out_taxids[: n.value] if tax else None)
+        return _sized_records(lambda po, pot, cap: (self.L.ukm_unik_decode(self.h, pb, nb, int(k), int(flags), int(taxid_bytes), po, pot, cap,
+                                                                           C.byref(n)), n.value), body, tax, out, out_taxids, nb == 0)
 
     def unik_encode(self, keys, k, flags, taxids=None, taxid_bytes=0, out=None):
         """the body unik::Writer writes for these records, as uint8.  Without `out` it is sized by unik_encode_bound."""
@@ -738,14 +751,12 @@ class Context:
         assert taxids is None or nt == n
         args = (int(file_taxid), n, int(k), int(bool(hashed)), int(fmt))
         m = C.c_uint64()
-        if out is None:
-            rc = self.L.ukm_view(self.h, pk, pt, *args, None, 0, C.byref(m))
-            if rc != ERR_CAPACITY:
-                _check(rc)
-            out = _empty_like_kind(keys, m.value, np.uint8)
-        po, cap, _ = _ptr(out, np.uint8)
-        _check(self.L.ukm_view(self.h, pk, pt, *args, po, cap if n else 0, C.byref(m)), m.value)
-        return out[: m.value]
+
+        def call(o):
+            po, cap, _ = _ptr(o, np.uint8)
+            return self.L.ukm_view(self.h, pk, pt, *args, po, cap if n else 0, C.byref(m)), m.value
+        out, size = _sized(call, out, lambda need: _empty_like_kind(keys, need, np.uint8))
+        return out[:size]
 
     def dump(self, text, *, k, flags=0, out=None, out_taxids=None):
         """the records of k-mer text (`unikmer dump`, the strict grammar of include/unikmer_hip.h): (keys, taxids), taxids None
@@ -763,20 +774,8 @@ class Context:
                 except FormatError as e:
                     e.bad_off = bad.value
                     raise
-            return rc
-        if out is None:
-            rc = call(None, None, 0)
-            if rc != ERR_CAPACITY:
-                _check(rc)
-            out = _empty_like_kind(text, n.value, np.uint64)
-        po, cap, _ = _ptr(out, np.uint64)
-        if tax and out_taxids is None:
-            out_taxids = _empty_like_kind(text, cap, np.uint32)
-        pot, ncap, _ = _ptr(out_taxids if tax else None, np.uint32)
-        if tax:
-            cap = min(cap, ncap)
-        _check(call(po, pot, cap if nb else 0), n.value)
-        return out[: n.value], (out_taxids[: n.value] if tax else None)
+            return rc, n.value
+        return _sized_records(call, text, tax, out, out_taxids, nb == 0)
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
