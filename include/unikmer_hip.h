@@ -179,7 +179,11 @@ int ukm_last_route(ukm_ctx *ctx);
  *      "lb_watchdogs" = times a look-back watchdog fired in this context (a tile's predecessor did not publish: the
  *      launch was repeated with ticketed tile ids, or a chained inter / diff fold fell back to the synchronous fold),
  *      "ticket_latched" = 1 once that has happened: every later look-back kernel of the context takes its tile ids from
- *      tickets, for the context's lifetime (0 otherwise; option "force_ticket" does not show here). */
+ *      tickets, for the context's lifetime (0 otherwise; option "force_ticket" does not show here),
+ *      "inflate_candidates" / "inflate_segments" = of the last ukm_inflate: the offsets it found behind a marker 00 00 FF FF
+ *      (offset 0 included), and how many of them began a segment on the chain: the rest were false hits;
+ *      "inflate_cp_walk_us" = the device time, in microseconds, of that call's second walk over the chain (the checkpoints):
+ *      the part of its write side that is not the write pass (0 where the call ended before it). */
 int ukm_ctx_set_option(ukm_ctx *ctx, const char *key, long long value);
 int ukm_ctx_unset_option(ukm_ctx *ctx, const char *key);
 int ukm_ctx_get_option(ukm_ctx *ctx, const char *key, long long *value, int *is_set);
@@ -463,6 +467,37 @@ int ukm_deflate(ukm_ctx *ctx, const uint8_t *src, uint64_t n_bytes, uint32_t fla
                 uint64_t *n_out, uint32_t *crc32);
 uint64_t ukm_deflate_bound(uint64_t n_bytes, uint32_t flags);
 uint32_t ukm_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* ---- inflate: read back what ukm_deflate wrote (and what zlib writes under Z_HUFFMAN_ONLY with a flush per chunk) without
+ *      one host thread.  src [n_bytes] (host or device, any alignment) is a raw RFC 1951 fragment that starts at a block
+ *      boundary on a byte boundary: the caller has taken off the gzip header, the trailer and anything in front.  The call
+ *      inflates the longest prefix it understands and says where it stopped; the caller goes on from there with zlib
+ *      (inflateSetDictionary with the last 32 KiB of output).
+ *      It understands NON-FINAL blocks of all three types -- stored (at any bit position), fixed and dynamic Huffman --
+ *      whose symbols are literals and end-of-block only.  It stops IN FRONT OF the first block that has BFINAL = 1 (even an
+ *      empty one), has BTYPE = 11, contains a length symbol (257 or above), has LEN != ~NLEN, has an over-subscribed or
+ *      incomplete code where zlib refuses that, or runs past n_bytes.  None of these is an error: the device never judges a
+ *      stream, zlib meets the same block next and reports it in its own words.
+ *      *n_consumed is always a block start on a byte boundary: offset 0, the byte behind a stored block that began on a byte
+ *      boundary, or the byte behind an empty stored block (the marker 00 00 FF FF); a run of bit-packed blocks counts only
+ *      as a whole, up to the empty stored block that closes it.  *n_out is the inflated size of exactly
+ *      src[0, *n_consumed).  *n_consumed == 0 with *n_out == 0 is UKM_OK: that is what a zlib level-6 stream gives.
+ *      *crc32 is in/out as in ukm_deflate: on entry the CRC-32 of the bytes in front of `out` in the caller's stream, on
+ *      exit (UKM_OK only) the CRC-32 of those bytes followed by out[0, *n_out).
+ *      out == NULL with out_cap == 0 is the size query; too small an out_cap: UKM_ERR_CAPACITY with the need in *n_out,
+ *      *n_consumed set, and nothing has been written to out.  Nothing outside out[0, *n_out) is ever written.  The output
+ *      is a pure function of src.  n_bytes == 0: UKM_OK, nothing consumed.  flags must be 0.
+ *      ukm_inflate_bound (pure host code): 8 * n_bytes, a literal costs at least one bit -- a worst case that nobody
+ *      should allocate: ask for the size, or take it from the gzip trailer.
+ *      Limits: a marker-to-marker segment that inflates to 2^31 bytes or more ends the device's part in front of the block
+ *      that crosses that size, and so do 256 consecutive segments that inflate to 2^32 bytes together; only long runs of
+ *      stored blocks get there.  A segment is decoded by one lane, so it also ends in front of the block that takes it beyond
+ *      2^20 literals of Huffman blocks or beyond 2^20 blocks: a Huffman-only stream that never flushes is zlib's from there.
+ *      After a call ukm_last_kernel_ms reports the step between the size side and the write side (the scan over the
+ *      chain's sizes and its read-back), ukm_last_call_ms the whole call. */
+int ukm_inflate(ukm_ctx *ctx, const uint8_t *src, uint64_t n_bytes, uint32_t flags, uint8_t *out, uint64_t out_cap,
+                uint64_t *n_out, uint64_t *n_consumed, uint32_t *crc32);
+uint64_t ukm_inflate_bound(uint64_t n_bytes);
 
 /* ---- k-mer text: replace the record loop of view.go:163-218 (everything except -g) and the line loop of dump.go:128-315
  *      (the paths that do not hash).  Byte buffers need no alignment; out_cap and *n_out of ukm_view are in BYTES; the size

@@ -1,5 +1,5 @@
 // ukm_bytes.h — what the kernels that read or write unaligned byte streams share (ukm_unik.hip: .unik bodies, ukm_text.hip:
-// k-mer text, ukm_deflate.hip: deflate blocks): a range of bytes to and from an LDS image as aligned 16-byte words,
+// k-mer text, ukm_deflate.hip and ukm_inflate.hip: deflate blocks): a range of bytes to and from an LDS image as aligned 16-byte words,
 // big-endian fields, and the size-then-write protocol of the calls whose output size is known only after a pass over the
 // input (below: SizeScan).  Workgroups of NT threads; the block scan is ukm_device.h's block_excl_scan_u32<NT>, the
 // library's one.  Everything has internal linkage: each source that includes this gets kernels of its own.

@@ -114,6 +114,9 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "setop_offs_stale") == 0) *value = c->stat_setop_offs_stale;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "lb_watchdogs") == 0) *value = c->stat_lb_watchdogs;
+    else if (strcmp(key, "inflate_candidates") == 0) *value = c->stat_inflate_candidates;
+    else if (strcmp(key, "inflate_segments") == 0) *value = c->stat_inflate_segments;
+    else if (strcmp(key, "inflate_cp_walk_us") == 0) *value = c->stat_inflate_cp_walk_us;
     else if (strcmp(key, "ticket_latched") == 0) *value = c->ticket_latched ? 1 : 0;
     else if (strcmp(key, "workspace_bytes") == 0) {
         u64 t = 0;

@@ -58,12 +58,7 @@ __global__ __launch_bounds__(NT) void dfl_sum_kernel(const u8 *src, u64 n_bytes,
     const int shift = load_image(src, chunk * (u64)DFL_CHUNK, len, s_img, tid);
     for (int i = tid; i < DFL_WAVES * H::LIT_SYMS; i += NT) s_hist[i] = 0;
     for (int i = tid; i < DFL_META / 4; i += NT) s_len32[i] = 0;
-    s_tab[tid] = H::crc_table_entry((u32)tid);
-    if (tid < 16) {  // x^(8 * 2^tid): what 2^tid more bytes multiply a CRC by
-        u32 p = H::CRC_X8;
-        for (int i = 0; i < tid; i++) p = H::crc_mul(p, p);
-        s_pow[tid] = p;
-    }
+    H::crc_lds_tables(s_tab, s_pow, tid);
     if (tid == 0) s_crc = s_used = 0;
     __syncthreads();
     // histogram: the image's 4-byte words, bytes outside [shift, shift + len) masked; a copy of the bins per wave
@@ -83,12 +78,7 @@ __global__ __launch_bounds__(NT) void dfl_sum_kernel(const u8 *src, u64 n_bytes,
         const u32 lo = (u32)tid * DFL_VT;
         if (lo < len) {
             const u32 hi = lo + DFL_VT < len ? lo + DFL_VT : len;
-            u32 c = 0;
-            for (u32 p = lo; p < hi; p++) c = s_tab[(c ^ B[p]) & 255u] ^ (c >> 8);
-            const u32 behind = len - hi;
-            for (int k = 0; k < 16; k++)
-                if ((behind >> k) & 1u) c = H::crc_mul(c, s_pow[k]);
-            atomicXor(&s_crc, c);
+            atomicXor(&s_crc, H::crc_slice(B, lo, hi, len, s_tab, s_pow));
         }
     }
     __syncthreads();

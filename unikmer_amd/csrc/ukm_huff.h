@@ -1,6 +1,7 @@
 // ukm_huff.h — what ukm_deflate.hip's kernels and its host code share, compiled for host and device alike (and, with a
 // plain C++ compiler, into tests/deflate_units.cpp): length-limited Huffman code lengths, canonical deflate codes, the
-// header of a dynamic block of literals, and the arithmetic of CRC-32 (RFC 1951 3.2.2, 3.2.7; RFC 1952 8).
+// header of a dynamic block of literals, and the arithmetic of CRC-32 (RFC 1951 3.2.2, 3.2.7; RFC 1952 8).  The CRC part,
+// with the workgroup's slice routine, is ukm_inflate.hip's too.
 //
 // Code lengths: Huffman, then repair -- what zlib's gen_bitlen does.  The used symbols are sorted by (frequency, symbol);
 // the two-queue merge (sorted leaves, internal nodes in creation order) builds the tree in O(n); the depths of the leaves
@@ -249,6 +250,28 @@ UKM_HD uint32_t crc_table_entry(uint32_t b) {
     for (int i = 0; i < 8; i++) b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
     return b;
 }
+#if defined(__HIPCC__)
+// A workgroup's raw CRC (zero register, no inversion) of len < 65536 bytes in LDS, from per-thread slices (ukm_deflate.hip: a
+// chunk of the source; ukm_inflate.hip: a tile of the output).  tab[256], pow[16]: LDS, filled by 256 threads in front of a
+// barrier; crc_slice: the raw CRC of B[lo, hi) times x^(8 * the bytes behind it): the XOR over all slices is the CRC of B.
+__device__ inline void crc_lds_tables(uint32_t *tab, uint32_t *pow, int tid) {
+    tab[tid] = crc_table_entry((uint32_t)tid);
+    if (tid < 16) {  // x^(8 * 2^tid): what 2^tid more bytes multiply a CRC by
+        uint32_t p = CRC_X8;
+        for (int i = 0; i < tid; i++) p = crc_mul(p, p);
+        pow[tid] = p;
+    }
+}
+__device__ inline uint32_t crc_slice(const uint8_t *B, uint32_t lo, uint32_t hi, uint32_t len, const uint32_t *tab, const uint32_t *pow) {
+    uint32_t c = 0;
+    for (uint32_t p = lo; p < hi; p++) c = tab[(c ^ B[p]) & 255u] ^ (c >> 8);
+    const uint32_t behind = len - hi;
+    for (int k = 0; k < 16; k++)
+        if ((behind >> k) & 1u) c = crc_mul(c, pow[k]);
+    return c;
+}
+#endif
+
 // The CRC-32 (as zlib's crc32 returns it) of A followed by B, from crc(A), the RAW CRC of B -- zero initial register, no final
 // inversion -- and B's length: the register is linear in (register, data).
 UKM_HD uint32_t crc_append_raw(uint32_t crc_a, uint32_t raw_b, uint64_t len_b) {

@@ -160,6 +160,8 @@ struct ukm_ctx {
     std::map<std::string, std::string> knobs, opts;
     bool env_live = false;
     // statistics a host or a test may ask for (ukm_ctx_get_stat)
+    u64 stat_inflate_cp_walk_us = 0;  // of the last ukm_inflate: device time of the second walk (inf_cp_kernel), microseconds
+    u64 stat_inflate_candidates = 0, stat_inflate_segments = 0;  // of the last ukm_inflate: offsets behind a marker (and 0); segments on the chain
     u64 stat_grep_route = 0;  // membership shape of the last ukm_grep: 1 queries in LDS, 2 sorted queries behind a prefix directory, 3 taxid bitmap, 0 no kernel
     u64 stat_punion_attempts = 0;  // base sets the last probe union / counting probes built (2: the retry with 4 x the files ran)
     u64 stat_punion_flags = 0;     // the flag word (ctl[1], PU_FLAG_*) the most recent probe pass of this context left

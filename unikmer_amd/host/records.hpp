@@ -20,12 +20,20 @@ static const bool DEVICE_VIEW_DEFAULT = false, DEVICE_DUMP_DEFAULT = true;
 // UNIKMER_DEVICE_GZIP=1 asks for it, UNIKMER_HOST_GZIP=1 keeps zlib everywhere.  --compression-level 0, text outputs and the
 // commands without a device (num, info, concat, head) stay on zlib whatever is said.
 static const bool DEVICE_GZIP_DEFAULT = false;
+// And for the gzip of a .unik INPUT (load_unik): zlib reads the header, the compressed body is uploaded and inflated on the
+// device (ukm_inflate) straight into the buffer ukm_unik_decode reads, where the device codec is on and the file is a regular
+// gzip file whose body is Huffman-only blocks -- what the device gzip above writes.  Any other file goes
+// through zlib as before.  UNIKMER_DEVICE_GUNZIP=1 asks for it, UNIKMER_HOST_GUNZIP=1 keeps zlib everywhere; stdin and the
+// commands without a device stay on zlib whatever is said.  UNIKMER_GUNZIP_REPORT=1: one line per input file on stderr,
+// "gunzip: <path>: device <bytes of the file the device's part ends at> of <file size> bytes" or "... host (<reason>)".
+static const bool DEVICE_GUNZIP_DEFAULT = false;
 struct Options {
     bool compress = true, compact = false, ignore_taxid = false, skip_file_check = false;
     int level = -1, gpu = 0;
     bool device_codec = DEVICE_CODEC_DEFAULT;  // .unik bodies through ukm_unik_decode / ukm_unik_encode (load_unik, write_unik)
     bool device_view = DEVICE_VIEW_DEFAULT, device_dump = DEVICE_DUMP_DEFAULT;  // view / dump text through ukm_view / ukm_dump
     bool device_gzip = DEVICE_GZIP_DEFAULT;    // compressed .unik outputs through ukm_deflate (write_unik, write_following)
+    bool device_gunzip = DEVICE_GUNZIP_DEFAULT, gunzip_report = false;  // gzip .unik inputs through ukm_inflate (load_unik)
     u32 max_taxid = 0xFFFFFFFFu;
     string data_dir;
 };
@@ -52,6 +60,10 @@ static Options get_options(const Args &a) {
     const char *hg = getenv("UNIKMER_HOST_GZIP"), *dg = getenv("UNIKMER_DEVICE_GZIP");
     if (dg && dg[0] == '1') o.device_gzip = true;
     if (hg && hg[0] == '1') o.device_gzip = false;
+    const char *hu = getenv("UNIKMER_HOST_GUNZIP"), *du = getenv("UNIKMER_DEVICE_GUNZIP"), *ru = getenv("UNIKMER_GUNZIP_REPORT");
+    if (du && du[0] == '1') o.device_gunzip = true;
+    if (hu && hu[0] == '1') o.device_gunzip = false;
+    o.gunzip_report = ru && ru[0] == '1';
     return o;
 }
 // util-cli.go:192-264 : files from the command line plus the optional list file; "-" = stdin
@@ -158,29 +170,95 @@ struct Loaded {
     bool has_taxid = false;
     bool per_record() const { return has_taxid && h.is_include_taxid(); }
 };
+// the records of a body in one piece (host or device memory), decoded by ukm_unik_decode into L's host vectors (a
+// device-resident Loaded is the follow-up)
+static void decode_body(ukm_ctx *c, const string &file, const unik::Header &h, const uint8_t *body, u64 nbody, Loaded &L) {
+    const bool tx = L.per_record();
+    u64 n = 0, guess = h.number == ~0ull ? 0 : std::min<u64>(h.number, nbody);  // (a record takes more than a byte)
+    const int rc = call_grow(UKM_ERR_CAPACITY, guess, &n, [&](u64 cap, u64 *m) {
+        L.codes.resize(cap); if (tx) L.taxids.resize(cap);
+        return ukm_unik_decode(c, body, nbody, h.k, h.flag, h.taxid_bytes, cap ? L.codes.data() : nullptr,
+                               cap && tx ? L.taxids.data() : nullptr, cap, m);
+    });
+    if (rc == UKM_ERR_FORMAT)  // the Reader's own words
+        throw unik::Error(string(strstr(ukm_last_error(), "truncated record") ? "truncated record: " : "unexpected EOF: ") + file);
+    ck(rc);
+    L.codes.resize(n); if (tx) L.taxids.resize(n);
+}
+static bool codec_takes(const unik::Header &h) {  // (no file outside is written; the Reader's arithmetic decides)
+    return !(h.is_compact() && !h.is_sorted() && (h.k < 1 || h.k > 32));
+}
+// The device gunzip path: false with the reason in `why` where the file is to go through zlib.  The inflated body never
+// crosses to the host: ukm_inflate writes it into the device buffer ukm_unik_decode reads.
+static bool load_unik_device_gunzip(const string &file, const Options &o, ukm_ctx *c, Loaded &L, string &why, u64 *upto, u64 *size) {
+    unik::GzInput g;
+    why = g.open(file);
+    if (!why.empty()) return false;
+    if (!codec_takes(g.h)) { why = "a layout the device codec does not take"; return false; }
+    const u64 n = g.body_end - g.body_at;
+    u64 cap = g.body_total();
+    if (!cap) { why = "nothing to inflate, or a size the trailer cannot mean"; return false; }
+    std::unique_ptr<DevMem> body(new DevMem(c, cap));
+    u64 n_out = 0, consumed = 0;
+    uint32_t crc = g.header_crc;
+    {
+        DevMem src(c, n);
+        ck(ukm_copy(c, src.p, g.file.data() + g.body_at, n));
+        int rc = ukm_inflate(c, (const uint8_t *)src.p, n, 0, (uint8_t *)body->p, cap, &n_out, &consumed, &crc);
+        if (rc == UKM_ERR_CAPACITY) {  // ISIZE is the size modulo 2^32
+            body.reset();
+            cap = n_out;
+            body.reset(new DevMem(c, cap));
+            crc = g.header_crc;
+            rc = ukm_inflate(c, (const uint8_t *)src.p, n, 0, (uint8_t *)body->p, cap, &n_out, &consumed, &crc);
+        }
+        ck(rc);
+    }
+    if (consumed == 0) { why = "no block the device takes (a stream with matches)"; return false; }
+    vector<uint8_t> last((size_t)std::min<u64>(n_out, 32768)), tail;
+    if (!last.empty()) ck(ukm_copy(c, last.data(), (const uint8_t *)body->p + (n_out - last.size()), last.size()));
+    why = g.finish(consumed, n_out, crc, last.data(), last.size(), &tail);
+    if (!why.empty()) return false;
+    if (n_out + tail.size() > cap) {
+        std::unique_ptr<DevMem> more(new DevMem(c, n_out + tail.size()));
+        if (n_out) ck(ukm_copy(c, more->p, body->p, n_out));
+        body.swap(more);
+    }
+    if (!tail.empty()) ck(ukm_copy(c, (uint8_t *)body->p + n_out, tail.data(), tail.size()));
+    L.h = g.h;
+    L.has_taxid = !o.ignore_taxid && g.h.has_taxid_info();
+    *upto = g.body_at + consumed;
+    *size = g.file.size();
+    vector<uint8_t>().swap(g.file);
+    decode_body(c, file, g.h, (const uint8_t *)body->p, n_out + tail.size(), L);
+    return true;
+}
 static Loaded load_unik(const string &file, const Options &o) {
+    bool own = false;
+    string why = "device gunzip is off";
+    if (o.device_gunzip) {  // (only here is a context made before the file has been looked at)
+        Loaded L;
+        u64 upto = 0, size = 0;
+        ukm_ctx *c = codec_ctx(o, &own);
+        if (!c) why = "no device codec";
+        else if (load_unik_device_gunzip(file, o, c, L, why, &upto, &size)) {
+            if (o.gunzip_report) fprintf(stderr, "gunzip: %s: device %llu of %llu bytes\n", file.c_str(), (unsigned long long)upto, (unsigned long long)size);
+            if (own) ck(ukm_ctx_trim(c));
+            if (L.has_taxid && !L.per_record()) L.file_taxid = L.h.global_taxid;
+            return L;
+        }
+    }
+    if (o.gunzip_report) fprintf(stderr, "gunzip: %s: host (%s)\n", file.c_str(), why.c_str());
     unik::Reader r(file);
     Loaded L;
     L.h = r.h;
     L.has_taxid = !o.ignore_taxid && r.h.has_taxid_info();
-    bool own = false;
     ukm_ctx *c = codec_ctx(o, &own);
-    if (c && r.h.is_compact() && !r.h.is_sorted() && (r.h.k < 1 || r.h.k > 32)) c = nullptr;  // (no such file is written; the Reader's arithmetic decides)
+    if (c && !codec_takes(r.h)) c = nullptr;
     if (c) {
-        // the body in one piece, decoded by ukm_unik_decode into the host vectors (a device-resident Loaded is the follow-up)
         vector<uint8_t> body;
         r.read_body(body);
-        const bool tx = L.per_record();
-        u64 n = 0, guess = r.h.number == ~0ull ? 0 : std::min<u64>(r.h.number, body.size());  // (a record takes more than a byte)
-        const int rc = call_grow(UKM_ERR_CAPACITY, guess, &n, [&](u64 cap, u64 *m) {
-            L.codes.resize(cap); if (tx) L.taxids.resize(cap);
-            return ukm_unik_decode(c, body.data(), body.size(), r.h.k, r.h.flag, r.h.taxid_bytes, cap ? L.codes.data() : nullptr,
-                                   cap && tx ? L.taxids.data() : nullptr, cap, m);
-        });
-        if (rc == UKM_ERR_FORMAT)  // the Reader's own words
-            throw unik::Error(string(strstr(ukm_last_error(), "truncated record") ? "truncated record: " : "unexpected EOF: ") + file);
-        ck(rc);
-        L.codes.resize(n); if (tx) L.taxids.resize(n);
+        decode_body(c, file, r.h, body.data(), body.size(), L);
         if (own) ck(ukm_ctx_trim(c));
     } else {
         r.read_all(L.codes, L.per_record() ? &L.taxids : nullptr);

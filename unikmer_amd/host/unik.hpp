@@ -234,6 +234,43 @@ static inline int byte_len(uint64_t v) {
     return n;
 }
 
+// The header, from anything that has InStream's read / must_read: the file's stream (Reader), or the header's bytes as zlib
+// inflated them (GzInput).  The one statement of the layout on the reading side.
+template <class In>
+static inline void read_header_from(In &in, Header &h, const std::string &path) {
+    uint8_t b[64];
+    if (in.read(b, 8) != 8 || memcmp(b, ".unikmer", 8) != 0) throw Error("invalid binary format: " + path);
+    in.must_read(b, 4);
+    h.main_version = b[0]; h.minor_version = b[1]; h.k = b[2];
+    if (h.main_version != 5) throw Error("version mismatch (need v5.x): " + path);
+    in.must_read(b, 4); h.flag = (uint32_t)get_be(b, 4);
+    in.must_read(b, 8); h.number = get_be(b, 8);
+    in.must_read(b, 4); h.global_taxid = (uint32_t)get_be(b, 4);
+    in.must_read(b, 4); h.taxid_bytes = b[0];
+    if (h.taxid_bytes < 1 || h.taxid_bytes > 4) throw Error("bad taxid byte length: " + path);
+    in.must_read(b, 4);
+    const uint32_t dl = (uint32_t)get_be(b, 4);
+    if (dl > 1024) throw Error("description too long: " + path);
+    h.description.resize(dl);
+    if (dl) in.must_read(&h.description[0], dl);
+    in.must_read(b, 4); h.scale = (uint32_t)get_be(b, 4);
+    in.must_read(b, 8); h.max_hash = get_be(b, 8);
+    in.must_read(b, 52);
+}
+struct MemStream {  // bytes in memory behind InStream's two calls
+    const uint8_t *p;
+    size_t n, at = 0;
+    size_t read(void *dst, size_t want) {
+        const size_t got = std::min(want, n - at);
+        memcpy(dst, p + at, got);
+        at += got;
+        return got;
+    }
+    void must_read(void *dst, size_t want) {
+        if (read(dst, want) != want) throw Error("unexpected EOF");
+    }
+};
+
 // ---- Reader -------------------------------------------------------------------------------------
 class Reader {
   public:
@@ -321,32 +358,165 @@ class Reader {
         in_.must_read(b, h.taxid_bytes);
         return (uint32_t)get_be(b, h.taxid_bytes);
     }
-    void read_header() {
-        uint8_t b[64];
-        if (in_.read(b, 8) != 8 || memcmp(b, ".unikmer", 8) != 0) throw Error("invalid binary format: " + path_);
-        in_.must_read(b, 4);
-        h.main_version = b[0]; h.minor_version = b[1]; h.k = b[2];
-        if (h.main_version != 5) throw Error("version mismatch (need v5.x): " + path_);
-        in_.must_read(b, 4); h.flag = (uint32_t)get_be(b, 4);
-        in_.must_read(b, 8); h.number = get_be(b, 8);
-        in_.must_read(b, 4); h.global_taxid = (uint32_t)get_be(b, 4);
-        in_.must_read(b, 4); h.taxid_bytes = b[0];
-        if (h.taxid_bytes < 1 || h.taxid_bytes > 4) throw Error("bad taxid byte length: " + path_);
-        in_.must_read(b, 4);
-        const uint32_t dl = (uint32_t)get_be(b, 4);
-        if (dl > 1024) throw Error("description too long: " + path_);
-        h.description.resize(dl);
-        if (dl) in_.must_read(&h.description[0], dl);
-        in_.must_read(b, 4); h.scale = (uint32_t)get_be(b, 4);
-        in_.must_read(b, 8); h.max_hash = get_be(b, 8);
-        in_.must_read(b, 52);
-    }
+    void read_header() { read_header_from(in_, h, path_); }
 
     InStream in_;
     std::string path_;
     uint64_t prev_ = 0, second_ = 0;
     uint32_t second_taxid_ = 0;
     bool have_second_ = false;
+};
+
+// ---- a gzip input whose body is inflated elsewhere ----------------------------------------------------
+// The host's part of reading a file that OutStream's device-gzip mode wrote (or Python's save(deflate="device")) without
+// zlib inflating the body: open() takes the gzip framing off and lets zlib read the .unik header up to the sync-flush marker
+// behind it; the caller hands file[body_at, body_end) to ukm_inflate, which says how far it got; finish() lets zlib read what
+// is left behind that point (the final block; a Writer's trailing odd record) with the output so far as its dictionary, and
+// checks the trailer.  Both return "" or the reason why the file is to be read through InStream instead: nothing here is an
+// error, the host path meets the same bytes and names what is wrong with them.
+struct GzInput {
+    std::vector<uint8_t> file;
+    Header h;
+    std::vector<uint8_t> header_bytes;  // the .unik header as it was inflated
+    size_t body_at = 0, body_end = 0;   // file[body_at, body_end): the deflate stream behind the header's marker, in front of the trailer
+    uint32_t header_crc = 0;            // CRC-32 of header_bytes: what the body's CRC is chained to
+
+    static constexpr size_t HEADER_FIXED = 36, HEADER_TAIL = 64, DESC_MAX = 1024;
+
+    std::string open(const std::string &path) {
+        if (path == "-") return "stdin";
+        FILE *f = fopen(path.c_str(), "rb");
+        if (!f) return "cannot be opened";
+        bool ok = fseek(f, 0, SEEK_END) == 0;
+        const long size = ok ? ftell(f) : -1;
+        ok = ok && size >= 0 && fseek(f, 0, SEEK_SET) == 0;
+        if (ok) {
+            file.resize((size_t)size);
+            ok = fread(file.data(), 1, file.size(), f) == file.size();
+        }
+        fclose(f);
+        if (!ok) return "not a regular file";
+        return open_bytes();
+    }
+    // the same on `file` as it stands
+    std::string open_bytes() {
+        if (file.size() < 2 || file[0] != 0x1f || file[1] != 0x8b) return "not gzip";
+        if (file.size() < 18 || file[2] != 8) return "not a gzip member";
+        if (file[3] != 0) return "gzip header with FLG != 0";
+        body_end = file.size() - 8;
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2";
+        header_bytes.assign(HEADER_FIXED + DESC_MAX + HEADER_TAIL + 1, 0);
+        z.next_in = file.data() + 10;
+        z.avail_in = (uInt)std::min<size_t>(body_end - 10, 1u << 20);
+        z.next_out = header_bytes.data();
+        z.avail_out = (uInt)header_bytes.size();
+        size_t need = 0;
+        std::string why;
+        for (;;) {
+            const int rc = inflate(&z, Z_BLOCK);  // returns at every block boundary
+            if (rc != Z_OK) {
+                why = rc == Z_STREAM_END ? "the stream ends with the header's block" : std::string("the header: ") + (z.msg ? z.msg : "zlib stops");
+                break;
+            }
+            if (!need && z.total_out >= HEADER_FIXED) {
+                const uint64_t dl = get_be_(header_bytes.data() + 32, 4);
+                if (dl > DESC_MAX) {
+                    why = "description too long";
+                    break;
+                }
+                need = HEADER_FIXED + (size_t)dl + HEADER_TAIL;
+            }
+            if ((need && z.total_out > need) || z.avail_out == 0) {
+                why = "the header does not end at a block boundary";
+                break;
+            }
+            // "a block just ended, not the last one, no unused bits", the header exactly out, and the marker just read
+            const bool boundary = (z.data_type & 128) && !(z.data_type & 64) && (z.data_type & 63) == 0;
+            if (need && z.total_out == need && boundary && z.total_in >= 4 && memcmp(z.next_in - 4, "\x00\x00\xff\xff", 4) == 0) break;
+            if (z.avail_in == 0) {
+                why = "the header does not end at a sync flush";
+                break;
+            }
+        }
+        body_at = 10 + (size_t)z.total_in;
+        inflateEnd(&z);
+        if (!why.empty()) return why;
+        header_bytes.resize(need);
+        header_crc = (uint32_t)crc32(0, header_bytes.data(), (uInt)need);
+        return parse_header();
+    }
+    // the size of the inflated body, the trailing bytes included, from the trailer's ISIZE (the total modulo 2^32): the
+    // smallest that n compressed bytes can inflate to -- stored framing takes less than a byte per 4096 -- and 0 where that
+    // is above 8 bytes per byte
+    uint64_t body_total() const {
+        const uint64_t n = body_end - body_at, low = n - std::min<uint64_t>(n, n / 4096 + 64);
+        uint64_t total = (uint32_t)(isize() - (uint32_t)header_bytes.size());
+        while (total < low) total += 1ull << 32;
+        return total > 8 * n ? 0 : total;
+    }
+    // consumed, n_out, crc: what ukm_inflate gave for file[body_at, body_end) with *crc32 = header_crc on entry; last: the
+    // last min(n_out, 32768) bytes of its output.  *tail: the bytes that follow them in the body.
+    std::string finish(uint64_t consumed, uint64_t n_out, uint32_t crc, const uint8_t *last, size_t n_last, std::vector<uint8_t> *tail) {
+        tail->clear();
+        if (consumed > body_end - body_at) return "consumed more than there is";
+        std::vector<uint8_t> dict;
+        if (n_last < 32768) dict.assign(header_bytes.end() - (std::ptrdiff_t)std::min<size_t>(header_bytes.size(), 32768 - n_last), header_bytes.end());
+        dict.insert(dict.end(), last, last + n_last);
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2";
+        std::string why;
+        if (!dict.empty() && inflateSetDictionary(&z, dict.data(), (uInt)dict.size()) != Z_OK) why = "inflateSetDictionary";
+        size_t at = body_at + (size_t)consumed;
+        int rc = Z_OK;
+        while (why.empty() && rc != Z_STREAM_END) {
+            const size_t have = tail->size();
+            tail->resize(have + (1u << 16));
+            z.next_out = tail->data() + have;
+            z.avail_out = 1u << 16;
+            z.next_in = file.data() + at;
+            z.avail_in = (uInt)std::min<size_t>(body_end - at, 1u << 30);
+            const uInt fed = z.avail_in;
+            rc = inflate(&z, Z_NO_FLUSH);
+            at += fed - z.avail_in;
+            tail->resize(have + ((1u << 16) - z.avail_out));
+            if (rc == Z_STREAM_END) break;
+            if (rc != Z_OK && rc != Z_BUF_ERROR) why = std::string("behind the device's part: ") + (z.msg ? z.msg : "zlib stops");
+            else if (at == body_end && z.avail_out != 0) why = "the stream does not end in front of the trailer";
+        }
+        inflateEnd(&z);
+        if (!why.empty()) return why;
+        if (at != body_end) return "bytes behind the deflate stream (a second member?)";
+        crc = (uint32_t)crc32(crc, tail->data(), (uInt)tail->size());
+        if (crc != (uint32_t)get_le_(file.data() + body_end, 4)) return "CRC-32 mismatch";
+        if ((uint32_t)(header_bytes.size() + n_out + tail->size()) != isize()) return "size mismatch";
+        return "";
+    }
+    uint32_t isize() const { return (uint32_t)get_le_(file.data() + body_end + 4, 4); }
+
+  private:
+    static uint64_t get_be_(const uint8_t *p, int n) {
+        uint64_t v = 0;
+        for (int i = 0; i < n; i++) v = (v << 8) | p[i];
+        return v;
+    }
+    static uint64_t get_le_(const uint8_t *p, int n) {
+        uint64_t v = 0;
+        for (int i = n - 1; i >= 0; i--) v = (v << 8) | p[i];
+        return v;
+    }
+    // the Reader's own routine on the inflated bytes; what it refuses goes the host's way and is refused there, with the path
+    std::string parse_header() {
+        MemStream m{header_bytes.data(), header_bytes.size()};
+        try {
+            read_header_from(m, h, "");
+        } catch (const Error &e) {
+            return e.what();
+        }
+        return m.at == header_bytes.size() ? "" : "the header's size";
+    }
 };
 
 // ---- Writer -------------------------------------------------------------------------------------

@@ -48,6 +48,7 @@ SYMBOLS = [
     "ukm_unik_decode", "ukm_unik_encode", "ukm_unik_encode_bound",
     "ukm_view", "ukm_view_bound", "ukm_dump",
     "ukm_deflate", "ukm_deflate_bound", "ukm_crc32_combine",
+    "ukm_inflate", "ukm_inflate_bound",
 ]
 
 
@@ -197,6 +198,9 @@ def load():
     L.ukm_deflate.argtypes = [vp, vp, u64, u32, vp, u64, pu64, C.POINTER(u32)]
     L.ukm_deflate_bound.argtypes = [u64, u32]
     L.ukm_deflate_bound.restype = u64
+    L.ukm_inflate.argtypes = [vp, vp, u64, u32, vp, u64, pu64, pu64, C.POINTER(u32)]
+    L.ukm_inflate_bound.argtypes = [u64]
+    L.ukm_inflate_bound.restype = u64
     L.ukm_crc32_combine.argtypes = [u32, u32, u64]
     L.ukm_crc32_combine.restype = u32
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
@@ -332,6 +336,12 @@ DEFLATE_FINAL, DEFLATE_GZIP = 1, 2   # include/unikmer_hip.h: UKM_DEFLATE_*
 def deflate_bound(n_bytes, final=False, gzip=False):
     """bytes Context.deflate writes at most for n_bytes of input; pure host code"""
     return int(load().ukm_deflate_bound(int(n_bytes), (DEFLATE_FINAL if final else 0) | (DEFLATE_GZIP if gzip else 0)))
+
+
+def inflate_bound(n_bytes):
+    """8 * n_bytes: what n_bytes of deflate blocks inflate to at most under Context.inflate (a literal costs at least one
+    bit) -- a worst case that nobody should allocate: ask for the size, or take it from the gzip trailer; pure host code"""
+    return int(load().ukm_inflate_bound(int(n_bytes)))
 
 
 def crc32_combine(crc_a, crc_b, len_b):
@@ -741,6 +751,30 @@ class Context:
         po, cap, _ = _ptr(out, np.uint8)
         _check(self.L.ukm_deflate(self.h, pd, n, flags, po, cap, C.byref(m), C.byref(c)), m.value)
         return out[: m.value], int(c.value)
+
+    # ---- inflate (the gzip reader in front of a .unik body) ----
+    def inflate(self, data, crc=0, out=None):
+        """(bytes_out, consumed, crc): the longest prefix of `data` (uint8: a raw deflate fragment that starts at a block
+        boundary on a byte boundary) that is non-final blocks of literals -- what Context.deflate writes -- inflated where
+        the input lives.  consumed: the bytes of data that prefix takes, always a block start on a byte boundary; go on from
+        there with zlib.decompressobj(-15, zdict=<the last 32 KiB of output>).  consumed == 0 is no error: a stream with
+        matches gives it.  crc in: zlib.crc32 of what precedes bytes_out in the caller's stream, out: of that followed by
+        bytes_out.  Without `out` the size is asked for first; too small an `out`: CapacityError with .needed and
+        .consumed."""
+        pd, n, k1 = _ptr(data, np.uint8)
+        m, used = C.c_uint64(), C.c_uint64()
+        c = C.c_uint32(int(crc) & 0xFFFFFFFF)
+
+        def call(o):
+            po, cap, _ = _ptr(o, np.uint8)
+            c.value = int(crc) & 0xFFFFFFFF
+            return self.L.ukm_inflate(self.h, pd, n, 0, po, cap if o is not None else 0, C.byref(m), C.byref(used), C.byref(c)), m.value
+        try:
+            out, size = _sized(call, out, lambda need: _empty_like_kind(data, need, np.uint8))
+        except CapacityError as e:
+            e.consumed = int(used.value)
+            raise
+        return out[:size], int(used.value), int(c.value)
 
     # ---- k-mer text (`unikmer view` / `unikmer dump`) ----
     def view(self, keys, taxids=None, file_taxid=0, *, k, hashed=False, fmt=VIEW_KMER, out=None):

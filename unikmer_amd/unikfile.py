@@ -1,6 +1,7 @@
 """`.unik` files for the Python user: the header is read and written here, the body goes through the device codec
-(Context.unik_decode / unik_encode).  gzip inflate is the `gzip` module's, one host thread, and so is deflate unless
-save() is told deflate="device" (Context.deflate).
+(Context.unik_decode / unik_encode).  gzip inflate is the `gzip` module's, one host thread, unless load() is told
+inflate="device" (Context.inflate: files written by save(deflate="device") or by the driver under UNIKMER_DEVICE_GZIP);
+deflate is the `gzip` module's unless save() is told deflate="device" (Context.deflate).
 
 The header layout is the one unikmer_amd/host/unik.hpp states (unik::Reader::read_header, unik::Writer::write_header),
 big-endian throughout:
@@ -8,6 +9,7 @@ big-endian throughout:
     | taxid bytes u8, 3 x 0 | description length u32 | description | scale u32 | max hash u64 | 52 reserved zero bytes
 """
 import gzip
+import io
 import struct
 import zlib
 
@@ -65,10 +67,94 @@ def header_bytes(h):
             + struct.pack(">I", len(desc)) + desc + struct.pack(">IQ", h.get("scale", 1), h.get("max_hash", UNKNOWN_NUMBER)) + bytes(52))
 
 
-def load(ctx, path, device=True, ignore_taxid=False):
+MARKER = b"\x00\x00\xff\xff"   # an empty stored block behind its 3 header bits and padding: where a sync flush ends
+
+
+def _device_gunzip(ctx, path, device):
+    """(header, body) of a gzip file whose body Context.inflate takes, the body where `device` says; None: the file is for
+    the host path (which then also words whatever is wrong with it)"""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 18 or raw[:4] != b"\x1f\x8b\x08\x00":    # one member, deflate, FLG == 0
+        return None
+    src = raw[10:-8]
+    trailer_crc, isize = struct.unpack("<II", raw[-8:])
+    # zlib reads the .unik header, byte by byte, to the marker behind it (what save(deflate="device") and the driver write)
+    d, hb, at, need = zlib.decompressobj(-15), b"", 0, None
+    while True:
+        if at >= len(src) or d.eof:
+            return None
+        try:
+            hb += d.decompress(src[at: at + 1])
+        except zlib.error:
+            return None
+        at += 1
+        if need is None and len(hb) >= 36:
+            need = 36 + struct.unpack(">I", hb[32:36])[0] + 64
+        if len(hb) > (need if need is not None else 36 + 1024 + 64):
+            return None                                    # the header does not end at a block boundary
+        if len(hb) == need and src[at - 4: at] == MARKER:
+            break
+    try:
+        h = _read_header(io.BytesIO(hb), path)
+    except ValueError:
+        return None
+    frag = np.frombuffer(src, dtype=np.uint8)[at:]
+    n = len(frag)
+    # the body's size from ISIZE, the total modulo 2^32: the smallest that the fragment can inflate to (stored framing takes
+    # less than a byte per 4096), and not above 8 bytes per byte
+    total = (isize - len(hb)) % (1 << 32)
+    while total < n - n // 4096 - 64:
+        total += 1 << 32
+    if total > lib.inflate_bound(n):
+        return None
+    if device:
+        import torch
+        frag = torch.from_numpy(frag.copy()).cuda()
+    try:
+        body, consumed, crc = ctx.inflate(frag, crc=zlib.crc32(hb), out=lib._empty_like_kind(frag, total, np.uint8))
+    except lib.CapacityError as e:
+        body, consumed, crc = ctx.inflate(frag, crc=zlib.crc32(hb), out=lib._empty_like_kind(frag, e.needed, np.uint8))
+    if consumed == 0:
+        return None
+    nb = int(body.numel()) if lib._is_torch(body) else len(body)
+    last = body[max(0, nb - 32768):]
+    last = (last.cpu().numpy() if lib._is_torch(last) else last).tobytes()
+    zdict = (hb + last)[-32768:]
+    try:
+        d = zlib.decompressobj(-15, zdict=zdict)
+        tail = d.decompress(src[at + consumed:])
+    except zlib.error:
+        return None
+    if not d.eof or d.unused_data:                         # a second member, or a stream that does not end
+        return None
+    if zlib.crc32(tail, crc) != trailer_crc or (len(hb) + nb + len(tail)) & 0xFFFFFFFF != isize:
+        return None
+    body = body[:nb]
+    if tail:
+        t = np.frombuffer(tail, dtype=np.uint8)
+        if lib._is_torch(body):
+            import torch
+            body = torch.cat([body, torch.from_numpy(t.copy()).to(body.device)])
+        else:
+            body = np.concatenate([body, t])
+    return h, body
+
+
+def load(ctx, path, device=True, ignore_taxid=False, inflate="host"):
     """(header, keys, taxids): the records of a file, decoded on the device.  device=True: torch tensors on the GPU (the
     body is uploaded, 3-6 bytes a record for a sorted file), else numpy arrays.  taxids is None when the records carry none
-    (a global taxid is in the header) or with ignore_taxid."""
+    (a global taxid is in the header) or with ignore_taxid.  inflate="device": a gzip file written by
+    save(deflate="device") or by the driver's device gzip is inflated by Context.inflate -- with device=True the compressed
+    bytes are uploaded and the inflated body never crosses to the host; zlib reads the header, finishes the stream behind the
+    body and the trailer's CRC-32 and size are checked.  Any other file goes the host's way, as without it."""
+    if inflate not in ("host", "device"):
+        raise ValueError("inflate must be 'host' or 'device'")
+    got = _device_gunzip(ctx, path, device) if inflate == "device" else None
+    if got is not None:
+        h, body = got
+        keys, taxids = ctx.unik_decode(body, h["k"], h["flag"], h["taxid_bytes"], with_taxids=not ignore_taxid)
+        return h, keys, taxids
     with _open(path) as f:
         h = _read_header(f, path)
         body = np.frombuffer(f.read(), dtype=np.uint8)
