@@ -540,6 +540,44 @@ uint64_t ukm_view_bound(uint64_t n, int k, int hashed, uint32_t format);
 int ukm_dump(ukm_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int k, uint32_t flags, uint64_t *out_keys,
              uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out, uint64_t *bad_off);
 
+/* ---- FASTA/Q text: replace the byte loop of the sequence reader (bio/seqio/fastx as count.go:289-299 uses it; this
+ *      project's statement of it is host/seqtext.hpp: parse_fastx, and the call is held to it byte for byte).  text [n_bytes]
+ *      (host or device, any alignment) starts at a record boundary: the start of a file, or where an earlier call's
+ *      *n_consumed pointed.  The call handles the longest prefix inside the device's grammar and says where it stopped; it
+ *      never judges a file: what deviates is met by the host parser next and reported in its words.  It produces what a
+ *      FastxSink sees for text[0, *n_consumed): out_bases = the kept sequence bytes, concatenated; out_rec_off[i] and
+ *      out_rec_off[i + 1] bound record i there (out_rec_off[0] = 0, out_rec_off[*n_rec] = *n_bases; empty records are kept);
+ *      out_hdr_off[i] (may be NULL) = the offset in text of record i's '>' or '@': the caller reads the name from the text it
+ *      holds.  A line is the bytes between two LF.  A CR is dropped exactly when the next byte is an LF.  Space and TAB
+ *      inside sequence lines are dropped; every other byte of a sequence line is copied as it stands (the encode kernels
+ *      judge illegal bases).
+ *      FASTA: a line whose first byte is '>' opens a record; every other line adds to the open record.  In front of the first
+ *      header empty lines are skipped; any other line there stops the call: UKM_FASTX_STOP_GRAMMAR, *n_consumed = the start
+ *      of that line, *n_rec = 0.  Without UKM_FASTX_LAST the call consumes up to the start of the last header line and
+ *      returns UKM_FASTX_STOP_TAIL (*n_consumed == 0 where one record is longer than the text: call again with more).
+ *      FASTQ (UKM_FASTX_FASTQ; the CALLER decides, as parse_fastx does: FASTQ iff the first line of the FILE is non-empty
+ *      and begins with '@'): groups of exactly four lines from offset 0 -- a line that begins with '@'; a sequence line that
+ *      does not begin with '+' and holds no blank (it may be empty); a line that begins with '+'; a quality line at least as
+ *      long as the sequence line, both without their CR.  The first group that breaks a rule stops the call:
+ *      UKM_FASTX_STOP_GRAMMAR, *n_consumed = that group's first byte, where the host's state machine expects a header.
+ *      Without UKM_FASTX_LAST only groups whose four lines end in LF are consumed (UKM_FASTX_STOP_TAIL where bytes remain);
+ *      with it the last quality line may lack its LF, and lines behind the last whole group are a UKM_FASTX_STOP_GRAMMAR.
+ *      out_bases == NULL with bases_cap == 0 and rec_cap == 0 is the size query; either capacity too small:
+ *      UKM_ERR_CAPACITY with both needs in *n_bases / *n_rec, *n_consumed and *stop set, and nothing written.  Nothing outside
+ *      out_bases[0, *n_bases), out_rec_off[0, *n_rec] and out_hdr_off[0, *n_rec) is ever written.  n_bytes == 0: UKM_OK,
+ *      nothing consumed, UKM_FASTX_STOP_NONE.  Unknown flag bits: UKM_ERR_INVALID.  The output is a pure function of text and
+ *      flags.  All offsets are 64-bit; out_rec_off and out_hdr_off are 8-byte aligned.
+ *      After a call ukm_last_kernel_ms reports the scan between the size side and the write side (its read-backs included),
+ *      ukm_last_call_ms the whole call. */
+#define UKM_FASTX_FASTQ 1u   /* the text is FASTQ; without it, FASTA */
+#define UKM_FASTX_LAST 2u    /* text ends the input: the last record is complete, the last line may lack its LF */
+#define UKM_FASTX_STOP_NONE 0     /* everything was consumed */
+#define UKM_FASTX_STOP_TAIL 1     /* text[n_consumed, n_bytes) is an incomplete record: call again with more behind it */
+#define UKM_FASTX_STOP_GRAMMAR 2  /* text[n_consumed ..] begins something outside the device's grammar: the host parser's */
+int ukm_fastx(ukm_ctx *ctx, const uint8_t *text, uint64_t n_bytes, uint32_t flags, uint8_t *out_bases, uint64_t bases_cap,
+              uint64_t *out_rec_off /* [rec_cap + 1] */, uint64_t *out_hdr_off /* [rec_cap], may be NULL */, uint64_t rec_cap,
+              uint64_t *n_bases, uint64_t *n_rec, uint64_t *n_consumed, int *stop);
+
 /* ---- k-way merge: replaces mergeChunksFile (util-sort.go:227-606).  Streams are expected
  *      to be sorted (chunk files); an unsorted one is tolerated (the call then sorts the
  *      concatenation instead of merging).  mode/final_round as the reference's

@@ -3,6 +3,7 @@
 #include <condition_variable>
 #include <ctime>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <regex>
 #include <thread>
@@ -27,6 +28,9 @@ struct HostChunk {
     u64 cap = 0, nb = 0;
     vector<u64> off{0};
     vector<u32> wtax;  // -T: the taxid of every window of the chunk, in window order (count.go:334-344)
+    // the device parser's chunks (count_on_device, device_fastx): `bases` holds nb raw bytes of input file `file`
+    int file = 0;
+    bool first = false, last = false, fastq = false;  // the file's first / last chunk; its format, by parse_fastx's rule
     void reserve(u64 want) {  // grows the page-locked buffer (a record longer than a chunk)
         if (want <= cap) return;
         u64 ncap = std::max<u64>(want, cap + cap / 2);
@@ -51,6 +55,38 @@ struct ChunkPipe {
     int get_full() { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return !full.empty() || done; }); if (full.empty()) return -1; int i = full.front(); full.pop_front(); return i; }
     void put_free(int i) { { std::lock_guard<std::mutex> l(mu); free_.push_back(i); } cv.notify_all(); }
     void finish() { { std::lock_guard<std::mutex> l(mu); done = true; } cv.notify_all(); }
+    // The device parser met something outside its grammar in file `handover_file`: the reader thread, if it is still inside
+    // that file, parks (it reads no more and leaves `stream`) until the device thread has run the host parser over the rest.
+    int handover_file = -1;
+    bool parked = false, resume = false;
+    unik::InStream *stream = nullptr;
+    bool park_if_asked(int file, unik::InStream *in) {  // reader thread, in front of every read
+        std::unique_lock<std::mutex> l(mu);
+        if (handover_file != file) return false;
+        stream = in; parked = true;
+        cv.notify_all();
+        cv.wait(l, [&] { return resume; });
+        resume = parked = false; stream = nullptr;
+        return true;
+    }
+    void ask_handover(int file) { std::lock_guard<std::mutex> l(mu); handover_file = file; }
+    // the next full chunk, or -1 once the reader is parked (or done) and nothing is queued
+    int get_full_or_parked() { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return !full.empty() || parked || done; }); if (full.empty()) return -1; int i = full.front(); full.pop_front(); return i; }
+    void release_reader() { { std::lock_guard<std::mutex> l(mu); if (parked) resume = true; } cv.notify_all(); }
+};
+// what the host parser gives behind a handover: batches of records, flushed through `out` when they reach a chunk's size
+struct BatchFlushSink : FastxSink {
+    vector<uint8_t> bases;
+    vector<u64> off{0};
+    u64 chunk_bytes;
+    std::function<void(const uint8_t *, const u64 *, u64, u64)> out;  // (bases, off, records, bytes)
+    bool begin_record(const string &) override { return true; }
+    void add_seq(const char *p, size_t n) override { bases.insert(bases.end(), p, p + n); }
+    void end_record() override { off.push_back(bases.size()); if (bases.size() >= chunk_bytes) flush(); }
+    void flush() {
+        if (off.size() > 1) out(bases.data(), off.data(), off.size() - 1, bases.size());
+        bases.clear(); off.assign(1, 0);
+    }
 };
 struct ChunkSink : FastxSink {
     ChunkPipe &pipe;
@@ -119,7 +155,11 @@ struct DevArray {
 
 static u64 count_on_device(Gpu &g, int device, const vector<string> &files, const std::regex *skip_name, int k, bool canonical, bool circular,
                            bool hashed, u64 max_hash, bool linear, int uniq_mode, int key_bits, vector<u64> &codes,
-                           int minimizer_w = 0, const std::regex *tax_re = nullptr, vector<u32> *taxids_out = nullptr) {
+                           int minimizer_w = 0, const std::regex *tax_re = nullptr, vector<u32> *taxids_out = nullptr,
+                           bool device_fastx = false, bool fastx_report = false) {
+    // where the bytes are parsed: on the device (ukm_fastx) when asked for, except where a name per record is needed
+    const char *host_reason = !device_fastx ? "not asked for" : skip_name ? "-B" : tax_re ? "-T" : nullptr;
+    const bool raw = host_reason == nullptr;
     const char *ce = getenv("UNIKMER_CHUNK_MB");
     const u64 CH = (u64)(ce ? std::max(1, atoi(ce)) : 32) << 20;
     const double t0 = now_ms();
@@ -130,8 +170,34 @@ static u64 count_on_device(Gpu &g, int device, const vector<string> &files, cons
     std::thread parser([&]() {
         t_worker_thread = true;  // die() throws here instead of exiting under the main thread's HIP calls
         try {
+            if (raw) {  // the reader looks at no byte but the file's first: raw (inflated) bytes, CH to a chunk
+                for (int fi = 0; fi < (int)files.size(); fi++) {
+                    info("reading sequence file: %s", files[fi].c_str());
+                    unik::InStream in(files[fi]);
+                    bool first = true, fastq = false;
+                    for (;;) {
+                        if (pipe.park_if_asked(fi, &in)) break;
+                        const int i = pipe.get_free();
+                        HostChunk &h = ch[i];
+                        h.reset();
+                        h.nb = in.read(h.bases, CH);
+                        if (first) fastq = h.nb > 0 && h.bases[0] == '@';
+                        h.file = fi; h.first = first; h.last = h.nb < CH; h.fastq = fastq;
+                        first = false;
+                        const bool last = h.last;
+                        pipe.put_full(i);
+                        if (last) break;
+                    }
+                }
+                pipe.finish();
+                return;
+            }
             ChunkSink sink(pipe, ch, CH, skip_name, tax_re, k, circular);
-            for (auto &f : files) { info("reading sequence file: %s", f.c_str()); parse_fastx(f, sink); }
+            for (auto &f : files) {
+                info("reading sequence file: %s", f.c_str());
+                if (fastx_report) fprintf(stderr, "fastx: %s: host (%s)\n", f.c_str(), host_reason);
+                parse_fastx(f, sink);
+            }
             sink.flush();
         } catch (const std::exception &e) {
             std::lock_guard<std::mutex> l(pipe.mu);
@@ -181,8 +247,126 @@ static u64 count_on_device(Gpu &g, int device, const vector<string> &files, cons
         pipe.put_free(d.host);  // its upload is complete (the kernels waited for it): the parser may refill it
         d.host = -1;
     };
+    // ---- the device parser: a slot holds a chunk's raw bytes behind `pad` bytes of room, into which the bytes the previous
+    // call left unconsumed (an incomplete record) are copied device to device: the text of a call is tail + chunk
+    struct RawSlot { uint8_t *text = nullptr; u64 pad = 0, cap = 0, nb = 0; int host = -1; };
+    RawSlot rs[2];
+    DevMem *dbases = nullptr, *drec = nullptr;
+    u64 dbases_cap = 0, drec_cap = 0;
+    auto encode = [&](const uint8_t *bases, const u64 *off, u64 nrec, u64 nb) {  // host or device pointers
+        dcodes.ensure(n, n + nb);  // windows <= bases
+        u64 m = 0;
+        if (minimizer_w > 0) ck(ukm_minimizer(g.c, bases, off, nrec, k, minimizer_w, circular, max_hash, dcodes.p + n, nullptr, dcodes.cap - n, &m));
+        else if (hashed) ck(ukm_nthash(g.c, bases, off, nrec, k, canonical, circular, max_hash, dcodes.p + n, dcodes.cap - n, &m));
+        else ck(ukm_encode_kmers(g.c, bases, off, nrec, k, canonical, circular, dcodes.p + n, dcodes.cap - n, &m));
+        n += m;
+        total_bases += nb;
+    };
+    auto raw_room = [&](RawSlot &d, u64 pad, u64 data) {  // at least `pad` bytes in front of `data` bytes; keeps the chunk in it
+        if (d.text && d.pad >= pad && d.cap - d.pad >= data) return;
+        ck(ukm_copy_sync(g.c));  // (an upload into the old buffer may be on its way)
+        const u64 npad = d.text ? std::max<u64>((pad + pad / 2 + 15) & ~(u64)15, d.pad) : ((pad + 15) & ~(u64)15);
+        const u64 ndata = std::max<u64>(data, d.text ? d.cap - d.pad : 0);
+        void *p = nullptr;
+        ck(ukm_dev_alloc(g.c, npad + ndata, &p));
+        if (d.text) { if (d.nb) ck(ukm_copy(g.c, (uint8_t *)p + npad, d.text + d.pad, d.nb)); ukm_dev_free(g.c, d.text); }
+        d.text = (uint8_t *)p; d.pad = npad; d.cap = npad + ndata;
+    };
+    auto upload_raw = [&](RawSlot &d, int hi) {
+        HostChunk &h = ch[hi];
+        raw_room(d, 1 << 20, CH);
+        d.nb = h.nb;
+        if (h.nb) ck(ukm_copy_async(g.c, d.text + d.pad, h.bases, h.nb));
+        d.host = hi;
+        nchunks++;
+    };
+    u64 tail = 0, fpos = 0, fchunks = 0;  // unconsumed bytes in front of the current chunk; the file offset they start at
+    // chunk d through ukm_fastx and the encode kernels; nxt: the chunk already uploaded to `other` (-1: none), taken over by a handover
+    auto compute_raw = [&](RawSlot &d, RawSlot &other, int &nxt) {
+        HostChunk &h = ch[d.host];
+        const int fi = h.file;
+        const bool last = h.last, fastq = h.fastq;
+        if (h.first) { fpos = 0; fchunks = 0; }  // (records never span files: the tail is empty)
+        fchunks++;
+        const uint8_t *text = d.text + d.pad - tail;
+        const u64 nt = tail + d.nb;
+        u64 nb = 0, nrec = 0, used = 0;
+        int stop = UKM_FASTX_STOP_NONE;
+        if (nt) {
+            // the most a text can hold: every byte a base; a record in two bytes
+            const u64 rcap = nt / 2 + 1;
+            if (dbases_cap < nt) { delete dbases; dbases_cap = nt + nt / 8; dbases = new DevMem(g.c, dbases_cap); }
+            if (drec_cap < rcap) { delete drec; drec_cap = rcap + rcap / 8; drec = new DevMem(g.c, (drec_cap + 1) * 8); }
+            ck(ukm_fastx(g.c, text, nt, (fastq ? UKM_FASTX_FASTQ : 0u) | (last ? UKM_FASTX_LAST : 0u), (uint8_t *)dbases->p, dbases_cap,
+                         (u64 *)drec->p, nullptr, drec_cap, &nb, &nrec, &used, &stop));
+            if (nrec) encode((const uint8_t *)dbases->p, (const u64 *)drec->p, nrec, nb);
+        }
+        pipe.put_free(d.host);  // its upload is complete (the kernels waited for it): the reader may refill it
+        d.host = -1;
+        if (stop != UKM_FASTX_STOP_GRAMMAR) {
+            tail = nt - used;
+            fpos += used;
+            if (tail) {  // in front of the next chunk, device to device (a record longer than the room: the room grows)
+                raw_room(other, tail, CH);
+                ck(ukm_copy(g.c, other.text + other.pad - tail, text + used, tail));
+            }
+            if (last && fastx_report) fprintf(stderr, "fastx: %s: device, %llu chunk(s)\n", files[fi].c_str(), (unsigned long long)fchunks);
+            return;
+        }
+        // outside the device's grammar: the rest of the file -- what is left of this text, the chunks already read, the stream --
+        // goes through the host parser, from a byte at which its state machine expects a header
+        vector<char> mem(nt - used);
+        if (!mem.empty()) ck(ukm_copy(g.c, mem.data(), text + used, mem.size()));
+        tail = 0;
+        bool exhausted = last;
+        if (!exhausted) {
+            pipe.ask_handover(fi);
+            auto take = [&](int i) {
+                HostChunk &x = ch[i];
+                mem.insert(mem.end(), (const char *)x.bases, (const char *)x.bases + x.nb);
+                exhausted = x.last;
+                fchunks++;
+                pipe.put_free(i);
+            };
+            if (nxt >= 0) { ck(ukm_copy_sync(g.c)); other.host = -1; other.nb = 0; take(nxt); nxt = -1; }
+            while (!exhausted) {
+                const int i = pipe.get_full_or_parked();
+                if (i < 0) break;
+                nchunks++;
+                take(i);
+            }
+        }
+        BatchFlushSink sink;
+        sink.chunk_bytes = CH;
+        sink.out = encode;
+        parse_fastx(mem.data(), mem.size(), exhausted ? nullptr : pipe.stream, fastq, files[fi], sink);
+        sink.flush();
+        pipe.release_reader();
+        if (fastx_report)
+            fprintf(stderr, "fastx: %s: device, %llu chunk(s), host from byte %llu (grammar)\n", files[fi].c_str(), (unsigned long long)fchunks,
+                    (unsigned long long)(fpos + used));
+        if (nxt < 0) {  // the chunk that was on its way has been taken over: the next file's first
+            nxt = pipe.get_full();
+            if (nxt >= 0) upload_raw(other, nxt);
+        }
+    };
     int cur = 0;
     int hi = pipe.get_full();
+    if (raw) {
+        if (hi >= 0) upload_raw(rs[cur], hi);
+        while (hi >= 0) {
+            ck(ukm_copy_fence(g.c));    // kernels of the current chunk start after its upload
+            int nxt = pipe.get_full();  // (blocks while the reader is still filling it)
+            if (nxt >= 0) upload_raw(rs[cur ^ 1], nxt);
+            compute_raw(rs[cur], rs[cur ^ 1], nxt);
+            cur ^= 1;
+            hi = nxt;
+        }
+        for (auto &d : rs) if (d.text) ukm_dev_free(g.c, d.text);
+        delete dbases;
+        delete drec;
+        hi = -1;
+    }
     if (hi >= 0) upload(sl[cur], hi);
     while (hi >= 0) {
         ck(ukm_copy_fence(g.c));            // kernels of the current chunk start after its upload
@@ -293,7 +477,8 @@ static int cmd_count(int argc, char **argv) {
     if (a.has("seq-name-filter")) re_skip = std::regex(a.str("seq-name-filter"), std::regex::icase);
     if (parse_taxid) re_tax = std::regex(a.str("parse-taxid-regexp"));
     const u64 n = count_on_device(g, o.gpu, files, a.has("seq-name-filter") ? &re_skip : nullptr, k, canonical, circular, hashed, max_hash, linear,
-                                  uniq_mode, key_bits, codes, minimizer ? (int)minimizer_w : 0, parse_taxid ? &re_tax : nullptr, &taxids);
+                                  uniq_mode, key_bits, codes, minimizer ? (int)minimizer_w : 0, parse_taxid ? &re_tax : nullptr, &taxids,
+                                  o.device_fastx, o.fastx_report);
     u32 mode = 0;
     if (canonical) mode |= unik::UnikCanonical;
     if (parse_taxid) mode |= unik::UnikIncludeTaxID;

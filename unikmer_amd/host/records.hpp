@@ -27,6 +27,12 @@ static const bool DEVICE_GZIP_DEFAULT = false;
 // commands without a device stay on zlib whatever is said.  UNIKMER_GUNZIP_REPORT=1: one line per input file on stderr,
 // "gunzip: <path>: device <bytes of the file the device's part ends at> of <file size> bytes" or "... host (<reason>)".
 static const bool DEVICE_GUNZIP_DEFAULT = false;
+// And for the FASTA/Q input of `count` (cmd_count.hpp): the reader thread hands raw (inflated) bytes on, ukm_fastx parses
+// them where the encode kernels read, and what is outside its grammar goes to parse_fastx from the byte it names (DESIGN.md
+// 4.21).  UNIKMER_DEVICE_FASTX=1 asks for it, UNIKMER_HOST_FASTX=1 keeps the host parser; -B and -T need a name per record and
+// stay with the host parser whatever is said.  UNIKMER_FASTX_REPORT=1: one line per input file on stderr,
+// "fastx: <path>: device, <N> chunk(s)[, host from byte <B> (grammar)]" or "fastx: <path>: host (<reason>)".
+static const bool DEVICE_FASTX_DEFAULT = false;
 struct Options {
     bool compress = true, compact = false, ignore_taxid = false, skip_file_check = false;
     int level = -1, gpu = 0;
@@ -34,6 +40,7 @@ struct Options {
     bool device_view = DEVICE_VIEW_DEFAULT, device_dump = DEVICE_DUMP_DEFAULT;  // view / dump text through ukm_view / ukm_dump
     bool device_gzip = DEVICE_GZIP_DEFAULT;    // compressed .unik outputs through ukm_deflate (write_unik, write_following)
     bool device_gunzip = DEVICE_GUNZIP_DEFAULT, gunzip_report = false;  // gzip .unik inputs through ukm_inflate (load_unik)
+    bool device_fastx = DEVICE_FASTX_DEFAULT, fastx_report = false;        // the input of count through ukm_fastx (count_on_device)
     u32 max_taxid = 0xFFFFFFFFu;
     string data_dir;
 };
@@ -64,6 +71,10 @@ static Options get_options(const Args &a) {
     if (du && du[0] == '1') o.device_gunzip = true;
     if (hu && hu[0] == '1') o.device_gunzip = false;
     o.gunzip_report = ru && ru[0] == '1';
+    const char *hf = getenv("UNIKMER_HOST_FASTX"), *df = getenv("UNIKMER_DEVICE_FASTX"), *rf = getenv("UNIKMER_FASTX_REPORT");
+    if (df && df[0] == '1') o.device_fastx = true;
+    if (hf && hf[0] == '1') o.device_fastx = false;
+    o.fastx_report = rf && rf[0] == '1';
     return o;
 }
 // util-cli.go:192-264 : files from the command line plus the optional list file; "-" = stdin

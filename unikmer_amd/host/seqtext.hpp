@@ -85,10 +85,12 @@ struct FastxSink {
     virtual void add_seq(const char *p, size_t n) = 0;
     virtual void end_record() = 0;
 };
-static void parse_fastx(const string &file, FastxSink &sink) {
-    unik::InStream in(file);
+// The parser proper.  The bytes come from rd(dst, n) -> the number read, 0 at the end; fmt: -1 the first line decides (FASTQ
+// iff it is non-empty and begins with '@'), 0 FASTA, 1 FASTQ -- decided by whoever read the start of the file.
+template <class Read>
+static void parse_fastx_from(Read &&rd, const string &file, FastxSink &sink, int fmt) {
     vector<char> buf(1 << 20);
-    bool have = false, keep = false, fastq = false;
+    bool have = false, keep = false, fastq = fmt == 1;
     int fq_state = 0;  // 0 header, 1 seq, 3 qual
     u64 seq_len = 0, qual_len = 0;
     auto finish = [&]() {
@@ -117,9 +119,9 @@ static void parse_fastx(const string &file, FastxSink &sink) {
         if (!have) { if (l.empty()) return; die("invalid FASTA/Q format: %s", file.c_str()); }
         seq_line(l);
     };
-    bool first = true;
+    bool first = fmt < 0;
     for (;;) {
-        size_t n = in.read(buf.data(), buf.size());
+        size_t n = rd(buf.data(), buf.size());
         if (n == 0) break;
         size_t s0 = 0;
         for (size_t i = 0; i < n; i++) {
@@ -136,6 +138,19 @@ static void parse_fastx(const string &file, FastxSink &sink) {
     }
     if (!carry.empty()) { if (first) fastq = carry[0] == '@'; handle(carry); }
     finish();
+}
+static void parse_fastx(const string &file, FastxSink &sink) {
+    unik::InStream in(file);
+    parse_fastx_from([&](char *dst, size_t n) { return in.read(dst, n); }, file, sink, -1);
+}
+// the same from the middle of a file: mem[0, n_mem) -- bytes already in memory, starting where the parser expects a header --
+// followed by what `rest` (may be null) still holds, in the format already decided
+static void parse_fastx(const char *mem, size_t n_mem, unik::InStream *rest, bool fastq, const string &file, FastxSink &sink) {
+    size_t at = 0;
+    parse_fastx_from([&](char *dst, size_t n) -> size_t {
+        if (at < n_mem) { const size_t got = std::min(n, n_mem - at); memcpy(dst, mem + at, got); at += got; return got; }
+        return rest ? rest->read(dst, n) : 0;
+    }, file, sink, fastq ? 1 : 0);
 }
 struct BatchSink : FastxSink {
     SeqBatch &b;

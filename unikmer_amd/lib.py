@@ -22,6 +22,9 @@ UNIK_COMPACT, UNIK_SORTED, UNIK_INCLUDE_TAXID = 1, 4, 8   # header flag bits the
 VIEW_KMER, VIEW_KMER_CODE, VIEW_CODE, VIEW_KMER_TAXID, VIEW_TAXID, VIEW_FASTA, VIEW_FASTQ = range(7)
 VIEW_WITH_TAXID = 16
 DUMP_TAXID, DUMP_DECIMAL, DUMP_CANONICAL, DUMP_CANONICAL_ONLY = 1, 2, 4, 8
+# ukm_fastx flags and stop reasons (include/unikmer_hip.h: UKM_FASTX_*)
+FASTX_FASTQ, FASTX_LAST = 1, 2
+FASTX_STOP_NONE, FASTX_STOP_TAIL, FASTX_STOP_GRAMMAR = 0, 1, 2
 PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 F_MIX_TAXID, F_CMP_TAXID = 2, 4
@@ -49,6 +52,7 @@ SYMBOLS = [
     "ukm_view", "ukm_view_bound", "ukm_dump",
     "ukm_deflate", "ukm_deflate_bound", "ukm_crc32_combine",
     "ukm_inflate", "ukm_inflate_bound",
+    "ukm_fastx",
 ]
 
 
@@ -201,6 +205,7 @@ def load():
     L.ukm_inflate.argtypes = [vp, vp, u64, u32, vp, u64, pu64, pu64, C.POINTER(u32)]
     L.ukm_inflate_bound.argtypes = [u64]
     L.ukm_inflate_bound.restype = u64
+    L.ukm_fastx.argtypes = [vp, vp, u64, u32, vp, u64, vp, vp, u64, pu64, pu64, pu64, C.POINTER(i32)]
     L.ukm_crc32_combine.argtypes = [u32, u32, u64]
     L.ukm_crc32_combine.restype = u32
     L.ukm_minimizer.argtypes = [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, u64, pu64]
@@ -810,6 +815,43 @@ class Context:
                     raise
             return rc, n.value
         return _sized_records(call, text, tax, out, out_taxids, nb == 0)
+
+    # ---- FASTA/Q text (the input of `unikmer count`) ----
+    def fastx(self, text, *, fastq=False, last=True, out=None):
+        """(bases, rec_off, hdr_off, consumed, stop): the longest prefix of `text` (uint8, starting at a record boundary)
+        inside the device's FASTA / FASTQ grammar (include/unikmer_hip.h: ukm_fastx), parsed where the text lives.  bases:
+        the kept sequence bytes; rec_off [n_rec + 1]: record i is bases[rec_off[i]:rec_off[i + 1]]; hdr_off [n_rec]: where
+        record i's '>' / '@' stands in text; consumed: the bytes of text that prefix takes; stop: FASTX_STOP_*.  last=False:
+        more text follows, the incomplete record at the end is left to the next call.  out: (bases, rec_off, hdr_off) arrays
+        of the caller (rec_off one longer than hdr_off); without it the sizes are asked for first.  Too small: CapacityError
+        with .needed = (bases, records)."""
+        pt, n, k1 = _ptr(text, np.uint8)
+        flags = (FASTX_FASTQ if fastq else 0) | (FASTX_LAST if last else 0)
+        nb, nr, used = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        stop = C.c_int()
+
+        def call(o):
+            pb, bcap, _ = _ptr(o and o[0], np.uint8)
+            pr, rcap, _ = _ptr(o and o[1], np.uint64)
+            ph, hcap, _ = _ptr(o and o[2], np.uint64)
+            cap = min(rcap - 1, hcap) if o is not None else 0
+            return self.L.ukm_fastx(self.h, pt, n, flags, pb, bcap, pr, ph, max(cap, 0), C.byref(nb), C.byref(nr), C.byref(used), C.byref(stop))
+        if out is None:
+            rc = call(None)
+            if rc != ERR_CAPACITY:
+                _check(rc)
+            out = (_empty_like_kind(text, nb.value, np.uint8), _empty_like_kind(text, nr.value + 1, np.uint64),
+                   _empty_like_kind(text, nr.value, np.uint64))
+        rc = call(out)
+        if rc == ERR_CAPACITY:
+            try:
+                _check(rc)
+            except CapacityError as e:
+                e.needed = (int(nb.value), int(nr.value))
+                e.consumed, e.stop = int(used.value), int(stop.value)
+                raise
+        _check(rc)
+        return out[0][: nb.value], out[1][: nr.value + 1], out[2][: nr.value], int(used.value), int(stop.value)
 
     # ---- sort / scans ----
     def sort_u64(self, keys, key_bits=64):
