@@ -14,8 +14,9 @@ device-to-device copy of the text's bytes timed in the same run.  The results ar
 first 4 MB of each text.
 
 End to end: `unikmer count -k 31 -K -s` on text (1), uncompressed and gzipped, wall time of --e2e-runs runs behind one that
-is not counted: this build with UNIKMER_DEVICE_FASTX=1, with UNIKMER_HOST_FASTX=1, and --parent-bin (the parent commit's
-driver) when given; the outputs must be the same bytes.
+is not counted: this build with UNIKMER_DEVICE_FASTX=1 and with UNIKMER_HOST_FASTX=1, and --parent-bin (the parent commit's
+driver) when given, both ways as well (a parent from before the switch takes the host parser either way); the outputs must be
+the same bytes.
 """
 import argparse
 import gzip
@@ -186,7 +187,8 @@ def main():
     for path, kind in ((plain, "uncompressed"), (gz, "gzip")):
         sums = {}
         for label, exe, env in (("device_fastx", BIN, {"UNIKMER_DEVICE_FASTX": "1"}), ("host_fastx", BIN, {"UNIKMER_HOST_FASTX": "1"}),
-                                ("parent", a.parent_bin, {})):
+                                ("parent_device_fastx", a.parent_bin, {"UNIKMER_DEVICE_FASTX": "1"}),
+                                ("parent_host_fastx", a.parent_bin, {"UNIKMER_HOST_FASTX": "1"})):
             if exe is None:
                 continue
             env_all = {k: v for k, v in os.environ.items() if k not in SWITCHES}

@@ -6,9 +6,13 @@
 // flags and output-naming rules; all k-mer arithmetic that the reference does per record on
 // the CPU goes through the HIP library.  One translation unit, in layers:
 //   base.hpp, seqtext.hpp   device-free: errors, flags, paths, k-mer text, the FASTA/Q parser (tests/host_units.cpp)
+//   count_pipe.hpp          device-free: the chunk pipeline of count -- the pipe between the reader thread and the device thread,
+//                           the handover of a file to the host parser, the reader bodies, the double-buffered loop
+//                           (tests/count_pipe_units.cpp)
 //   records.hpp             .unik files <-> host vectors <-> library calls: the input loader and the shared steps
-//   cmd_count.hpp   count  (count.go)   FASTA/Q -> ukm_encode_kmers | ukm_nthash | ukm_minimizer -> ukm_sort_* -> ukm_unique;
-//                          the window values stay on the device from encode to the final set (chunked, double-buffered upload)
+//   cmd_count.hpp   count  (count.go)   FASTA/Q -> [ukm_fastx ->] ukm_encode_kmers | ukm_nthash | ukm_minimizer -> ukm_sort_* ->
+//                          ukm_unique; the window values stay on the device from encode to the final set.  A CountJob, the two
+//                          stages of count_pipe.hpp's loop (ParsedStage, RawStage), finish_count; count_on_device wires them
 //   cmd_setops.hpp  union / inter / diff / common -> ukm_union_ft / ukm_inter_ft / ukm_diff_ft / ukm_common_ft
 //   cmd_chunks.hpp  sort   (sort.go)    ukm_sort_u64 | ukm_sort_pairs -> ukm_unique(-u/-d); with -m, and for split / merge,
 //                          the chunk protocol: sorted chunk files -> ukm_merge_k_ft

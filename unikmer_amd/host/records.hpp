@@ -27,7 +27,7 @@ static const bool DEVICE_GZIP_DEFAULT = false;
 // commands without a device stay on zlib whatever is said.  UNIKMER_GUNZIP_REPORT=1: one line per input file on stderr,
 // "gunzip: <path>: device <bytes of the file the device's part ends at> of <file size> bytes" or "... host (<reason>)".
 static const bool DEVICE_GUNZIP_DEFAULT = false;
-// And for the FASTA/Q input of `count` (cmd_count.hpp): the reader thread hands raw (inflated) bytes on, ukm_fastx parses
+// And for the FASTA/Q input of `count` (cmd_count.hpp, count_pipe.hpp): the reader thread hands raw (inflated) bytes on, ukm_fastx parses
 // them where the encode kernels read, and what is outside its grammar goes to parse_fastx from the byte it names (DESIGN.md
 // 4.21).  UNIKMER_DEVICE_FASTX=1 asks for it, UNIKMER_HOST_FASTX=1 keeps the host parser; -B and -T need a name per record and
 // stay with the host parser whatever is said.  UNIKMER_FASTX_REPORT=1: one line per input file on stderr,
@@ -41,9 +41,18 @@ struct Options {
     bool device_gzip = DEVICE_GZIP_DEFAULT;    // compressed .unik outputs through ukm_deflate (write_unik, write_following)
     bool device_gunzip = DEVICE_GUNZIP_DEFAULT, gunzip_report = false;  // gzip .unik inputs through ukm_inflate (load_unik)
     bool device_fastx = DEVICE_FASTX_DEFAULT, fastx_report = false;        // the input of count through ukm_fastx (count_on_device)
+    u64 chunk_bytes = 32u << 20;  // UNIKMER_CHUNK_MB (default 32, at least 1): the bytes of a chunk of count's pipeline
     u32 max_taxid = 0xFFFFFFFFu;
     string data_dir;
 };
+// One switch of the environment: UNIKMER_DEVICE_<x>=1 turns it on, UNIKMER_HOST_<x>=1 turns it off and wins; where neither
+// is said every flag of the switch keeps its default.  report: UNIKMER_<x>_REPORT=1.
+static void env_switch(const string &x, std::initializer_list<bool *> flags, bool *report = nullptr) {
+    auto is_1 = [](const string &name) { const char *v = getenv(name.c_str()); return v && v[0] == '1'; };
+    if (is_1("UNIKMER_DEVICE_" + x)) for (bool *f : flags) *f = true;
+    if (is_1("UNIKMER_HOST_" + x)) for (bool *f : flags) *f = false;
+    if (report) *report = is_1("UNIKMER_" + x + "_REPORT");
+}
 static Options get_options(const Args &a) {
     Options o;
     g_verbose = a.has("verbose");
@@ -58,23 +67,13 @@ static Options get_options(const Args &a) {
     o.data_dir = a.has("data-dir") ? a.str("data-dir") : (env ? string(env) : (string(home ? home : ".") + "/.unikmer"));
     const char *g = getenv("UNIKMER_GPU");
     o.gpu = (int)a.num("gpu", g ? atoi(g) : 0);
-    const char *hc = getenv("UNIKMER_HOST_CODEC"), *dc = getenv("UNIKMER_DEVICE_CODEC");
-    if (dc && dc[0] == '1') o.device_codec = true;
-    if (hc && hc[0] == '1') o.device_codec = false;
-    const char *ht = getenv("UNIKMER_HOST_TEXT"), *dt = getenv("UNIKMER_DEVICE_TEXT");
-    if (dt && dt[0] == '1') o.device_view = o.device_dump = true;
-    if (ht && ht[0] == '1') o.device_view = o.device_dump = false;
-    const char *hg = getenv("UNIKMER_HOST_GZIP"), *dg = getenv("UNIKMER_DEVICE_GZIP");
-    if (dg && dg[0] == '1') o.device_gzip = true;
-    if (hg && hg[0] == '1') o.device_gzip = false;
-    const char *hu = getenv("UNIKMER_HOST_GUNZIP"), *du = getenv("UNIKMER_DEVICE_GUNZIP"), *ru = getenv("UNIKMER_GUNZIP_REPORT");
-    if (du && du[0] == '1') o.device_gunzip = true;
-    if (hu && hu[0] == '1') o.device_gunzip = false;
-    o.gunzip_report = ru && ru[0] == '1';
-    const char *hf = getenv("UNIKMER_HOST_FASTX"), *df = getenv("UNIKMER_DEVICE_FASTX"), *rf = getenv("UNIKMER_FASTX_REPORT");
-    if (df && df[0] == '1') o.device_fastx = true;
-    if (hf && hf[0] == '1') o.device_fastx = false;
-    o.fastx_report = rf && rf[0] == '1';
+    env_switch("CODEC", {&o.device_codec});
+    env_switch("TEXT", {&o.device_view, &o.device_dump});
+    env_switch("GZIP", {&o.device_gzip});
+    env_switch("GUNZIP", {&o.device_gunzip}, &o.gunzip_report);
+    env_switch("FASTX", {&o.device_fastx}, &o.fastx_report);
+    const char *mb = getenv("UNIKMER_CHUNK_MB");
+    o.chunk_bytes = (u64)(mb ? std::max(1, atoi(mb)) : 32) << 20;
     return o;
 }
 // util-cli.go:192-264 : files from the command line plus the optional list file; "-" = stdin
@@ -118,6 +117,30 @@ struct DevMem {
     ~DevMem() { if (p) ukm_dev_free(c, p); }
     DevMem(const DevMem &) = delete;
 };
+// Device memory that grows.  ensure(want): at least `want` bytes, the contents dropped -- the old memory is freed first and
+// want + want / 8 bytes are allocated (a buffer refilled chunk after chunk).  ensure(want, keep), keep > 0: the first `keep`
+// bytes stay -- at least twice the old size is allocated and they are copied (an array that is appended to).
+struct DevBuf {
+    ukm_ctx *c;
+    uint8_t *p = nullptr;
+    u64 cap = 0;
+    explicit DevBuf(ukm_ctx *ctx) : c(ctx) {}
+    DevBuf(ukm_ctx *ctx, u64 bytes) : c(ctx), cap(bytes) { void *q = nullptr; ck(ukm_dev_alloc(c, bytes, &q)); p = (uint8_t *)q; }  // exactly `bytes`
+    ~DevBuf() { if (p) ukm_dev_free(c, p); }
+    DevBuf(const DevBuf &) = delete;
+    void swap(DevBuf &o) { std::swap(c, o.c); std::swap(p, o.p); std::swap(cap, o.cap); }
+    template <class T> T *as() const { return (T *)p; }
+    void ensure(u64 want, u64 keep = 0) {
+        if (want <= cap) return;
+        if (!keep) DevBuf(c).swap(*this);
+        DevBuf grown(c, keep ? std::max<u64>(want, cap * 2) : want + want / 8);
+        if (keep) ck(ukm_copy(c, grown.p, p, keep));
+        swap(grown);
+    }
+};
+// page-locked host memory of a context as the two plain functions of count_pipe.hpp's ChunkAlloc (the cookie is the context)
+static void *pinned_alloc(void *ctx, u64 bytes) { void *p = nullptr; ck(ukm_host_alloc((ukm_ctx *)ctx, bytes, &p)); return p; }
+static void pinned_free(void *ctx, void *p) { ukm_host_free((ukm_ctx *)ctx, p); }
 
 // The context the device codec runs on: the command's own where it has made one already, else one made here on first use and
 // kept for the process (*own: the caller trims its workspace after the call, the command's context will want the memory).
