@@ -162,6 +162,13 @@ int ukm_last_route(ukm_ctx *ctx);
  *      the membership shape of the last ukm_grep (1 LDS table, 2 prefix directory, 3 taxid bitmap, 0 no kernel ran),
  *      "count_window_retries" = ukm_count calls of this context that ran their window pass twice (more windows passed the
  *      Scaled filter than the size estimate of the internal buffer allowed for; the second pass is sized exactly),
+ *      "window_route" = the kernel that wrote the windows of the context's most recent window pass (ukm_encode_kmers, ukm_nthash,
+ *      and the inner window pass of ukm_minimizer, ukm_count, ukm_locate and the map calls): 1 window_kernel (the general one),
+ *      2 stripwin_kernel (rolling strips, long records), 3 nthash_strip_kernel (rolling strips behind the Scaled filter).  It is
+ *      set to 0 when such a pass begins, so a pass that ends before any launch (no record, no window) shows 0,
+ *      "window_strip_declined" = launches of a strip kernel, over the context's life, that gave up -- more records under one
+ *      tile than stripwin_kernel's table holds, more candidates in one tile than nthash_strip_kernel's list -- so that the
+ *      general kernel answered the call (same result, one wasted launch),
  *      "punion_flags" = the flag word the most recent hash-probe pass of this context left (union, union of files with one
  *      taxid each, counting probes of `common`; 0 when none has run, and cleared when a call tries such a route, so that
  *      an attempt that declines in front of its pass shows 0 and not an earlier call's word): 1 PU_FLAG_UNSORTED a file is not sorted, 2

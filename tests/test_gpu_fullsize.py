@@ -321,8 +321,10 @@ def test_config5_sketch_1e10_bases_full_size(env, monkeypatch):
     torch.cuda.synchronize()
     monkeypatch.setenv("UKM_NTHASH_STRIP", "1")
     a = ctx.nthash(bases, reads, k, canonical=True, max_hash=mh, out=out_a)
+    assert ctx.stat("window_route") == 3     # (the strip kernel answered: no tile overflowed its candidate list)
     monkeypatch.setenv("UKM_NTHASH_STRIP", "0")
     b = ctx.nthash(bases, reads, k, canonical=True, max_hash=mh, out=out_b)
+    assert ctx.stat("window_route") == 1
     monkeypatch.delenv("UKM_NTHASH_STRIP", raising=False)
     assert a.numel() == b.numel() and bool((a == b).all())
     # canonical = min of two (nearly) independent uniform hashes: P(keep) = 1 - (1 - 1/scale)^2

@@ -672,9 +672,18 @@ def test_nthash_scaled_strip_kernel(ctx, O, monkeypatch, force):
             for canonical in (True, False):
                 if scale == 3 and (k not in (23, 51) or not canonical):
                     continue
+                gave_up = ctx.stat("window_strip_declined")
                 got = ctx.nthash(bases, cuts, k, canonical=canonical, max_hash=mh)
                 exp = O.count_windows(bases, cuts, k, hashed=True, canonical=canonical, max_hash=mh)
                 assert np.array_equal(got, exp), (k, scale, canonical)
+                gave_up = ctx.stat("window_strip_declined") - gave_up
+                if force == "1":
+                    # forced: the strip kernel wrote the result, or it was launched and gave up (a full candidate list)
+                    assert (ctx.stat("window_route"), gave_up) in ((3, 0), (1, 1)), (k, scale, canonical)
+                    if scale == 3:   # two windows in three are candidates
+                        assert gave_up == 1, (k, scale, canonical)
+                    elif k >= 23:    # at most 256 x 256 x 2 / 300 = 437 expected candidates per tile: the list holds 1024
+                        assert gave_up == 0, (k, scale, canonical)
         mh = O.max_hash(1000)
         assert np.array_equal(ctx.nthash(bases, reads, k, max_hash=mh), O.count_windows(bases, reads, k, hashed=True, max_hash=mh))
     # tiny inputs, a record exactly k long, an input shorter than one strip
@@ -688,7 +697,10 @@ def test_nthash_scaled_strip_kernel(ctx, O, monkeypatch, force):
     off = np.array([0, 300_000], dtype=np.uint64)
     h0 = O.count_windows(poly[:31], np.array([0, 31], dtype=np.uint64), 31, hashed=True)[0]
     for mh in (int(h0), int(h0) - 1):
+        gave_up = ctx.stat("window_strip_declined")
         assert np.array_equal(ctx.nthash(poly, off, 31, max_hash=mh), O.count_windows(poly, off, 31, hashed=True, max_hash=mh))
+        if force == "1":   # everything is a candidate: gives up; nothing is: the strip kernel answers
+            assert (ctx.stat("window_route"), ctx.stat("window_strip_declined") - gave_up) == ((1, 1) if mh == int(h0) else (3, 0))
     # a misaligned base pointer (view shifted by one byte)
     buf = np.concatenate([np.zeros(1, np.uint8), bases[:300_000]])
     sh = buf[1:]
@@ -730,11 +742,14 @@ def test_windows_strip_kernel_long_records(ctx, O, L, monkeypatch, force):
                     got = ctx.encode_kmers(bases, cuts, k, canonical=canonical)
                     exp = O.count_windows(bases, cuts, k, hashed=False, canonical=canonical)
                     assert np.array_equal(got, exp), ("codes", Ls, k, canonical, len(cuts))
+                    assert ctx.stat("window_route") == 2, ("codes", Ls, k, canonical, len(cuts))   # (9e6 bases: also the library's choice)
             for k in ((1, 2, 23, 32, 33, 50, 51, 64) if Ls is None else (51,)):
                 for canonical in (True, False):
                     got = ctx.nthash(bases, cuts, k, canonical=canonical)
                     exp = O.count_windows(bases, cuts, k, hashed=True, canonical=canonical)
                     assert np.array_equal(got, exp), ("nthash", Ls, k, canonical, len(cuts))
+                    if force == "1":
+                        assert ctx.stat("window_route") == 2, ("nthash", Ls, k, canonical, len(cuts))
     monkeypatch.delenv("UKM_WIN_STRIP_L", raising=False)
     # an illegal base is an error only when an emitted window holds it (kmers.ErrIllegalBase)
     bad = bases.copy()
@@ -756,9 +771,12 @@ def test_windows_strip_kernel_long_records(ctx, O, L, monkeypatch, force):
         got, gpos = ctx.minimizer(bases, long_cuts, k, w, with_pos=True)
         exp, epos = _oracle_minimizer_records(O, bases, long_cuts, k, w)
         assert np.array_equal(got, exp) and np.array_equal(gpos, epos)
-    # more records under one tile than the kernel's table holds: falls back to the general kernel
-    many = np.concatenate([np.arange(0, 40_000, 100, dtype=np.uint64), np.array([n], dtype=np.uint64)])
+    # more records under one tile than the kernel's table holds (40-base records across one tile of the default strip length:
+    # 409 of them, the table holds 254): falls back to the general kernel
+    many = np.concatenate([np.arange(0, 256 * 64 + 1, 40, dtype=np.uint64), np.array([n], dtype=np.uint64)])
+    gave_up = ctx.stat("window_strip_declined")
     assert np.array_equal(ctx.encode_kmers(bases, many, 21), O.count_windows(bases, many, 21))
+    assert ctx.stat("window_strip_declined") == gave_up + 1 and ctx.stat("window_route") == 1
     # a misaligned base pointer
     buf = np.concatenate([np.zeros(1, np.uint8), bases])
     off = np.array([0, n], dtype=np.uint64)
@@ -986,12 +1004,30 @@ def test_ticketed_fallback_other_kernels(O, L, monkeypatch, family):
                     for canonical in (True, False):
                         if scale == 3 and (k not in (23, 51) or not canonical):
                             continue
+                        gave_up = c.stat("window_strip_declined")
                         got = c.nthash(bases, cuts, k, canonical=canonical, max_hash=mh)
                         exp = O.count_windows(bases, cuts, k, hashed=True, canonical=canonical, max_hash=mh)
                         assert np.array_equal(got, exp), (k, scale, canonical)
+                        gave_up = c.stat("window_strip_declined") - gave_up
+                        if family == "nthash_strip_off":
+                            assert (c.stat("window_route"), gave_up) == (1, 0), (k, scale, canonical)
+                        else:   # as in test_nthash_scaled_strip_kernel: the strip kernel answered, or was launched and gave up
+                            assert (c.stat("window_route"), gave_up) in ((3, 0), (1, 1)), (k, scale, canonical)
+                            if scale == 3:
+                                assert gave_up == 1, (k, scale, canonical)
+                            elif k >= 23:
+                                assert gave_up == 0, (k, scale, canonical)
                 mh = O.max_hash(1000)
+                gave_up = c.stat("window_strip_declined")
                 assert np.array_equal(c.nthash(bases, reads, k, max_hash=mh),
                                       O.count_windows(bases, reads, k, hashed=True, max_hash=mh))
+                gave_up = c.stat("window_strip_declined") - gave_up
+                if family == "nthash_strip_off":
+                    assert (c.stat("window_route"), gave_up) == (1, 0), k
+                else:
+                    assert (c.stat("window_route"), gave_up) in ((3, 0), (1, 1)), k
+                    if k >= 23:
+                        assert gave_up == 0, k
     finally:
         c.close()
 

@@ -205,10 +205,13 @@ def test_nthash_sketch_strip_kernel_equals_general_kernel_large(env, monkeypatch
     reads = torch.arange(0, nb + 1, 150, dtype=torch.int64, device=dev)
     mh = ctx.max_hash(1000)
     torch.cuda.synchronize()
+    gave_up = ctx.stat("window_strip_declined")
     monkeypatch.setenv("UKM_NTHASH_STRIP", "1")
     a = ctx.nthash(bases, reads, 51, canonical=True, max_hash=mh).clone()
+    assert ctx.stat("window_route") == 3     # two algorithms only if the strip kernel answered this one ...
     monkeypatch.setenv("UKM_NTHASH_STRIP", "0")
     b = ctx.nthash(bases, reads, 51, canonical=True, max_hash=mh)
+    assert ctx.stat("window_route") == 1 and ctx.stat("window_strip_declined") == gave_up   # ... and the general kernel that one
     assert a.numel() == b.numel() and a.numel() > 1_000_000 and bool((a == b).all())
 
 
@@ -232,10 +235,13 @@ def test_window_strip_kernel_equals_general_kernel_large(env, monkeypatch):
     torch.cuda.synchronize()
     for fn, k in ((ctx.encode_kmers, 31), (ctx.nthash, 51)):
         for canonical in (True, False):
+            gave_up = ctx.stat("window_strip_declined")
             monkeypatch.setenv("UKM_WIN_STRIP", "1")
             a = fn(bases, off, k, canonical=canonical).clone()
+            assert ctx.stat("window_route") == 2, (k, canonical)     # two algorithms only if the strip kernel answered this one ...
             monkeypatch.setenv("UKM_WIN_STRIP", "0")
             b = fn(bases, off, k, canonical=canonical)
+            assert ctx.stat("window_route") == 1 and ctx.stat("window_strip_declined") == gave_up, (k, canonical)
             assert a.numel() == b.numel() and a.numel() > 990_000_000 and bool((a == b).all()), (k, canonical)
             if fn == ctx.encode_kmers and not canonical:
                 first = a[: cuts[1] - k + 1]
@@ -244,7 +250,7 @@ def test_window_strip_kernel_equals_general_kernel_large(env, monkeypatch):
             if canonical:
                 monkeypatch.delenv("UKM_WIN_STRIP", raising=False)   # the library's own choice (the strip kernel here)
                 c = fn(bases, off, k, canonical=canonical)
-                assert bool((c == a).all())
+                assert bool((c == a).all()) and ctx.stat("window_route") == 2
                 del c
             del a, b
 

@@ -10,6 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from conftest import synth_tree  # noqa: E402
+from test_gpu_window_limits import SW_NT, SW_REC, _records_per_tile  # noqa: E402  (the strip kernel's table, read from the source)
 
 pytestmark = pytest.mark.gpu
 
@@ -286,14 +287,26 @@ def test_random_windows_strip_kernels(env, seed, monkeypatch):
         monkeypatch.setenv("UKM_WIN_STRIP_L", Ls)
         k = int(rng.choice([1, 3, 15, 16, 17, 21, 31, 32]))
         canon = bool(rng.integers(0, 2))
-        assert np.array_equal(ctx.encode_kmers(bases, cuts, k, canonical=canon),
-                              O.count_windows(bases, cuts, k, canonical=canon)), (seed, it, "codes", k, canon, Ls, n)
+        # forced is checked, not assumed: at most 2 + 60 + 48 + 3 records in all, fewer than the strip kernel's table holds
+        # under ONE tile, so it never gives up; a call without any window ends before a launch (route 0)
+        assert len(cuts) - 1 <= SW_REC
+        gave_up = ctx.stat("window_strip_declined")
+        exp = O.count_windows(bases, cuts, k, canonical=canon)
+        assert np.array_equal(ctx.encode_kmers(bases, cuts, k, canonical=canon), exp), (seed, it, "codes", k, canon, Ls, n)
+        assert ctx.stat("window_route") == (2 if len(exp) else 0), (seed, it, "codes", k, canon, Ls, n)
         kh = int(rng.choice([1, 2, 16, 31, 32, 33, 51, 63, 64]))
-        assert np.array_equal(ctx.nthash(bases, cuts, kh, canonical=canon),
-                              O.count_windows(bases, cuts, kh, hashed=True, canonical=canon)), (seed, it, "nthash", kh, canon, Ls, n)
+        exp = O.count_windows(bases, cuts, kh, hashed=True, canonical=canon)
+        assert np.array_equal(ctx.nthash(bases, cuts, kh, canonical=canon), exp), (seed, it, "nthash", kh, canon, Ls, n)
+        assert ctx.stat("window_route") == (2 if len(exp) else 0), (seed, it, "nthash", kh, canon, Ls, n)
+        assert ctx.stat("window_strip_declined") == gave_up
+        n_hashes = len(exp)
         mh = O.max_hash(int(rng.choice([50, 300, 2000])))
         assert np.array_equal(ctx.nthash(bases, cuts, kh, canonical=canon, max_hash=mh),
                               O.count_windows(bases, cuts, kh, hashed=True, canonical=canon, max_hash=mh)), (seed, it, "scaled", kh)
+        # the sketch kernel was launched: it answered, or its candidate list overflowed (small k, N runs: equal hashes) and
+        # the general kernel answered
+        gave_up = ctx.stat("window_strip_declined") - gave_up
+        assert (ctx.stat("window_route"), gave_up) in ((3, 0), (1, 1), (0, 1)), (seed, it, "scaled", kh, ctx.stat("window_route"), gave_up)
         w = int(rng.choice([3, 15]))
         hs, ps = [], []
         for r in range(len(cuts) - 1):
@@ -307,6 +320,7 @@ def test_random_windows_strip_kernels(env, seed, monkeypatch):
         ep = np.concatenate(ps) if ps else np.empty(0, np.uint64)
         gh, gp = ctx.minimizer(bases, cuts, kh, w, with_pos=True)
         assert np.array_equal(gh, eh) and np.array_equal(gp, ep), (seed, it, "minimizer", kh, w)
+        assert ctx.stat("window_route") == (2 if n_hashes else 0), (seed, it, "minimizer", kh, w)   # (its inner ntHash pass)
 
 
 @pytest.mark.parametrize("seed", _seeds(4))
@@ -376,16 +390,23 @@ def test_strip_windows_on_ragged_reads(env, seed, monkeypatch):
     cuts = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
     n = int(cuts[-1])
     bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n)]
+    gave_up = ctx.stat("window_strip_declined")
     for Ls in ("64", "128"):
         monkeypatch.setenv("UKM_WIN_STRIP_L", Ls)
+        # the reads are through the STRIP kernel only while every tile's records fit its table: counted here as the kernel counts
+        per_tile = _records_per_tile(cuts, SW_NT * int(Ls))
+        assert SW_REC // 4 < per_tile.max() <= SW_REC, (seed, Ls, per_tile.max())
         for k in (9, 16, 17, 30, 31, 32):
             canon = bool(rng.integers(0, 2))
             assert np.array_equal(ctx.encode_kmers(bases, cuts, k, canonical=canon),
                                   O.count_windows(bases, cuts, k, canonical=canon)), (seed, "codes", k, canon, Ls)
+            assert ctx.stat("window_route") == 2, (seed, "codes", k, canon, Ls)
         for kh in (15, 33, 50, 51, 64):
             canon = bool(rng.integers(0, 2))
             assert np.array_equal(ctx.nthash(bases, cuts, kh, canonical=canon),
                                   O.count_windows(bases, cuts, kh, hashed=True, canonical=canon)), (seed, "nthash", kh, canon, Ls)
+            assert ctx.stat("window_route") == 2, (seed, "nthash", kh, canon, Ls)
+    assert ctx.stat("window_strip_declined") == gave_up
     # an illegal base in a read that is emitted / in one that is shorter than k
     monkeypatch.delenv("UKM_WIN_STRIP_L", raising=False)
     long_r = int(np.argmax(lens >= 80))
@@ -393,11 +414,13 @@ def test_strip_windows_on_ragged_reads(env, seed, monkeypatch):
     bad[int(cuts[long_r]) + 40] = ord("*")
     with pytest.raises(L.IllegalBaseError):
         ctx.encode_kmers(bad, cuts, 31)
+    assert ctx.stat("window_route") == 2     # (the strip kernel found it)
     short = np.flatnonzero((lens > 0) & (lens < 31))
     if len(short):
         bad = bases.copy()
         bad[int(cuts[short[0]])] = ord("*")
         assert np.array_equal(ctx.encode_kmers(bad, cuts, 31), O.count_windows(bad, cuts, 31))
+        assert ctx.stat("window_route") == 2
 
 
 @pytest.mark.parametrize("seed", _seeds(3))

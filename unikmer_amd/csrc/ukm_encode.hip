@@ -738,7 +738,11 @@ int run_strip_filter(ukm_ctx *c, const u8 *bases, const u64 *rec_off, u64 n_rec,
     UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
         return launch_tiles(nthash_strip_kernel<false>, nthash_strip_kernel<true>, ticket, ntiles, ST_NT, c->stream, p);
     }, res));
-    if (res[1] & ENC_FLAG_OVERFLOW) return UKM_OK;  // candidate list overflow: general kernel
+    if (res[1] & ENC_FLAG_OVERFLOW) {  // candidate list overflow: general kernel
+        c->stat_window_strip_declined++;
+        return UKM_OK;
+    }
+    c->stat_window_route = 3;
     *n_out = res[0];
     UKM_TRY(check_capacity(*n_out, out_cap));
     *done = true;
@@ -1092,7 +1096,11 @@ int run_strip_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off
         else hipLaunchKernelGGL(stripwin_kernel<false>, dim3((unsigned)ntiles), dim3(SW_NT), 0, c->stream, p);
         return UKM_OK;
     }, res));
-    if (res[1] & ENC_FLAG_OVERFLOW) return UKM_OK;  // a tile with more records than the table holds: general kernel
+    if (res[1] & ENC_FLAG_OVERFLOW) {  // a tile with more records than the table holds: general kernel
+        c->stat_window_strip_declined++;
+        return UKM_OK;
+    }
+    c->stat_window_route = 2;
     UKM_TRY(check_legal(res));
     *done = true;
     return UKM_OK;
@@ -1107,6 +1115,7 @@ int run_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, u64 
                 int canonical, int circular, u64 max_hash, u64 *out, u64 out_cap, u64 *n_out,
                 u64 total_bases, const u64 **win_off = nullptr, FusedHist *fused = nullptr) {
     *n_out = 0;
+    c->stat_window_route = 0;
     if (fused) fused->shift = -1;
     if (win_off) *win_off = nullptr;
     if (n_rec == 0 || total_bases == 0) return UKM_OK;
@@ -1164,6 +1173,7 @@ int run_windows(ukm_ctx *c, bool hash, const u8 *bases, const u64 *rec_off, u64 
         else return launch_tiles(window_kernel<true, true, false>, window_kernel<true, true, true>, ticket, ntiles, NT, c->stream, p);
         return UKM_OK;
     }, res));
+    c->stat_window_route = 1;
     UKM_TRY(check_legal(res));
     *n_out = filter ? res[0] : total_windows;
     return check_capacity(*n_out, out_cap);

@@ -163,6 +163,8 @@ struct ukm_ctx {
     u64 stat_inflate_cp_walk_us = 0;  // of the last ukm_inflate: device time of the second walk (inf_cp_kernel), microseconds
     u64 stat_inflate_candidates = 0, stat_inflate_segments = 0;  // of the last ukm_inflate: offsets behind a marker (and 0); segments on the chain
     u64 stat_grep_route = 0;  // membership shape of the last ukm_grep: 1 queries in LDS, 2 sorted queries behind a prefix directory, 3 taxid bitmap, 0 no kernel
+    u64 stat_window_route = 0;  // kernel that wrote the windows of the last call through run_windows: 1 window_kernel, 2 stripwin_kernel, 3 nthash_strip_kernel, 0 no launch
+    u64 stat_window_strip_declined = 0;  // strip kernel launches of this context that set ENC_FLAG_OVERFLOW (record table / candidate list): the general kernel answered
     u64 stat_punion_attempts = 0;  // base sets the last probe union / counting probes built (2: the retry with 4 x the files ran)
     u64 stat_punion_flags = 0;     // the flag word (ctl[1], PU_FLAG_*) the most recent probe pass of this context left
     u64 stat_count_window_retries = 0;  // ukm_count calls that repeated the window pass: its estimated buffer was too small
