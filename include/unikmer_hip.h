@@ -183,6 +183,8 @@ int ukm_last_route(ukm_ctx *ctx);
  *      tiles from the match counts a call before it left with the table, and so ran without the look-back,
  *      "setop_offs_stale" = such calls whose tiles counted otherwise (contents rewritten in place under an unchanged
  *      partition): the pass ran again with the look-back (after two in a row the context stops trying).  See ukm_setop2.
+ *      "setop_multi_fused" / "setop_multi_split" = ukm_setop2_multi calls of this context that were answered by the one
+ *      fused pass / by one ordinary pass per operation (a call that began fused and met duplicate codes counts as split),
  *      "lb_watchdogs" = times a look-back watchdog fired in this context (a tile's predecessor did not publish: the
  *      launch was repeated with ticketed tile ids, or a chained inter / diff fold fell back to the synchronous fold),
  *      "ticket_latched" = 1 once that has happened: every later look-back kernel of the context takes its tile ids from
@@ -657,6 +659,27 @@ int ukm_diff_ft(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *const
 int ukm_common_ft(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *const *taxids, const uint32_t *file_taxids,
                   const uint64_t *lens, int nstreams, uint32_t threshold, uint32_t flags, uint64_t *out_keys,
                   uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
+
+/* ---- two or three 2-way operations of ONE pair in a single pass: union (union.go:186-208), inter (inter.go:205-278) and
+ *      diff (diff.go:379-454) of the same two sorted files -- the reference's README workflow -- read A and B once and write
+ *      every requested result from that one merge.
+ *      bit (1u << UKM_OP_x) of `ops` asks for operation x; arrays below are indexed by UKM_OP_UNION / _INTER / _DIFF.
+ *      For every requested x, out_keys[x], out_taxids[x], n_out[x] and the status are exactly what ukm_setop2_ft with op = x,
+ *      the same inputs and flags, and out_cap[x] would give.  Host or device arrays, as there; out_cap[x] == 0 with NULL
+ *      arrays is a size query for x; entries of operations that were not requested are neither read nor written
+ *      (out_taxids itself may be NULL when no stream carries taxids).  ops == 0 or a bit above UKM_OP_DIFF: UKM_ERR_INVALID.
+ *      If any requested output does not fit the call returns UKM_ERR_CAPACITY, EVERY requested n_out[x] holds the size
+ *      needed and nothing is written at or behind out_cap[x] of any output.  An unsorted input: UKM_ERR_UNSORTED.
+ *      What runs fused: PLAIN codes (both taxid pointers NULL, both file taxids 0), at least two operations, na + nb > 0.
+ *      Per-record or per-file taxids, a single operation, and inputs with duplicate codes take one ordinary pass per
+ *      operation instead (same results; taxids inside the fused kernel are left to a later version).  The fused pass keeps
+ *      a partition table of its own and leaves the cache that consecutive ukm_setop2 calls share untouched.  Statistics
+ *      "setop_multi_fused" / "setop_multi_split" (ukm_ctx_get_stat): calls that ended on each route. */
+int ukm_setop2_multi(ukm_ctx *ctx, uint32_t ops,
+                     const uint64_t *a_keys, const uint32_t *a_taxids, uint32_t a_file_taxid, uint64_t na,
+                     const uint64_t *b_keys, const uint32_t *b_taxids, uint32_t b_file_taxid, uint64_t nb,
+                     uint32_t flags, uint64_t *const out_keys[3], uint32_t *const out_taxids[3],
+                     const uint64_t out_cap[3], uint64_t n_out[3]);
 int ukm_merge_k_ft(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *const *taxids, const uint32_t *file_taxids,
                    const uint64_t *lens, int nstreams, int mode, int final_round, uint64_t *out_keys,
                    uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);

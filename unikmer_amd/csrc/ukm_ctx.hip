@@ -112,6 +112,8 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "setop_part_stale") == 0) *value = c->stat_setop_part_stale;
     else if (strcmp(key, "setop_offs_hits") == 0) *value = c->stat_setop_offs_hits;
     else if (strcmp(key, "setop_offs_stale") == 0) *value = c->stat_setop_offs_stale;
+    else if (strcmp(key, "setop_multi_fused") == 0) *value = c->stat_setop_multi_fused;
+    else if (strcmp(key, "setop_multi_split") == 0) *value = c->stat_setop_multi_split;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "window_route") == 0) *value = c->stat_window_route;
     else if (strcmp(key, "window_strip_declined") == 0) *value = c->stat_window_strip_declined;

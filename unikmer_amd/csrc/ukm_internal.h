@@ -172,6 +172,8 @@ struct ukm_ctx {
     u64 stat_setop_part_stale = 0;  // ... whose cached table failed the verification: the partition ran after all
     u64 stat_setop_offs_hits = 0;   // ... of the hits: plain-key passes that took their tiles' output offsets from the cached match counts
     u64 stat_setop_offs_stale = 0;  // ... whose tiles counted otherwise (contents changed in place, partition intact): the pass ran again with the look-back
+    u64 stat_setop_multi_fused = 0;  // ukm_setop2_multi calls answered by the one fused pass
+    u64 stat_setop_multi_split = 0;  // ... by one ordinary pass per operation (taxids, one operation, duplicate codes)
 
     // Partition cache of the public 2-way set operation (ukm_setops.hip: run_setop_pass).  The merge-path table depends on
     // (A, B, |A|, |B|, tile size) only -- union, inter and diff of one pair share it -- so the context keeps the table of the
@@ -415,6 +417,10 @@ int ukm_dev_setop2(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na, cons
 int ukm_dev_setop2_ct(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u32 cta, u64 na, const u64 *b,
                       const u32 *tb, u32 ctb, u64 nb, u32 flags, u64 *out, u32 *tout, u64 out_cap,
                       u64 *n_out);
+// two or three operations of one pair (ops: 1 << UKM_OP_x each; the arrays are indexed by UKM_OP_x); flags may carry
+// UKM_F_INTERNAL_PART_CACHE for the passes of the split route
+int ukm_dev_setop2_multi(ukm_ctx *c, u32 ops, const u64 *a, const u32 *ta, u32 cta, u64 na, const u64 *b, const u32 *tb, u32 ctb,
+                         u64 nb, u32 flags, u64 *const out[3], u32 *const tout[3], const u64 out_cap[3], u64 n_out[3]);
 int ukm_dev_setop2_link(ukm_ctx *c, int op, const u64 *a, const u32 *ta, u64 na_max, const u64 *na_dev, const u64 *b,
                         const u32 *tb, u64 nb, u32 flags, u64 *out, u32 *tout, u64 out_cap, u64 *ctl, u32 cta = 0, u32 ctb = 0);
 // fill n words with one value on the context's stream (file taxids; ukm_scan.hip)

@@ -1332,6 +1332,167 @@ void setop_tile_kernel(SetopArgs p) {
 #endif
 }
 
+// ---- two or three operations of one pair from ONE merge (ukm_setop2_multi) ----------------------
+// Plain codes only.  The union's merge with CT masks decides everything: `mask` = the union's records, `mmask` = the
+// intersection's (a matched pair, at its A step), `amask & ~mmask` = the difference's.  The tiles publish their MATCH count
+// and one look-back over it places all outputs (setop_offset_of): inter at MP, diff at a_t - MP, union at d_t - MP + s_t.
+// Two compaction rounds through the tile's LDS image: the union's survivors, flushed; then inter's at [0, m) and diff's
+// behind them -- disjoint subsets of the tile's A records, so they fit where the union's have just left.
+// OPS = 1 << UKM_OP_x of every requested operation, at least two.  out / cap are indexed by UKM_OP_x.
+struct SetopMultiOut {
+    u64 *out[3];
+    u64 cap[3];
+};
+template <int OPS, bool TICKET, int NTH, int VT>
+__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(SETOP_WAVES, SETOP_WAVES)))
+void setop_multi_tile_kernel(SetopArgs p, SetopMultiOut mo) {
+    constexpr bool WU = (OPS >> UKM_OP_UNION) & 1, WI = (OPS >> UKM_OP_INTER) & 1, WD = (OPS >> UKM_OP_DIFF) & 1;
+    static_assert(OPS > 0 && OPS < 8 && (int)WU + (int)WI + (int)WD >= 2, "two or three of union / inter / diff");
+    static_assert(NTH * VT + 8 < (1 << 16), "two 16-bit sums in one word");
+    constexpr int TILE = NTH * VT;
+    constexpr int SLOTS = TILE + 8;
+    constexpr int NP = TilePairs<NTH, VT>::NP;
+    constexpr int NW = NTH / 64;
+    __shared__ __attribute__((aligned(16))) u64 s_keys[SLOTS];
+    __shared__ u32 s_scan[NW + 1];
+    __shared__ u32 s_scan_d[NW + 1];
+    __shared__ u64 s_misc[3];
+    const int tid = (int)threadIdx.x;
+#ifdef UKM_PROFILE_PHASES
+    u64 ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    u64 tlast = clock64();
+#endif
+    u64 tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
+    // (a ticket comes out of LDS, i.e. in a vector register, and the tile's whole geometry with it: said to be uniform --
+    //  and 32 bits wide, as the counter is -- it stays in scalar registers as the blockIdx form's does; the ticketed form
+    //  spilled 19 to 23 registers without this)
+    if (TICKET) tile = (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)tile);
+    PH(0);
+    if (tile >= p.ntiles) return;
+    const TileGeom g = tile_geom<NTH, VT>(p, tile);
+    u32 bad = 0;
+    const bool fast = tile_is_fast<NTH, VT>(p, g);  // workgroup-uniform
+    if (fast) {
+        tile_dma_fast<NTH, VT>(p, g, tid, s_keys);
+        __syncthreads();
+        PH(1);
+    } else {
+        u64 rk[2 * NP];
+        u32 rt[2 * NP], rr[2 * NP];
+        tile_load<false, false, NTH, VT>(p, g, tid, rk, rt, rr);
+        tile_to_lds<false, false, NTH, VT>(tid, rk, rt, rr, s_keys, nullptr, nullptr);
+        __syncthreads();
+        PH(1);
+        bad = tile_check_order<false, NTH, VT>(g, tid, rk, rr, s_keys, nullptr);
+    }
+    u64 ok[VT];
+    u32 ot[VT], tbm[VT];  // (unused without taxids)
+    u32 need = 0, mask, amask = 0, mmask = 0;
+    int ia0 = 0, ib0 = 0;
+    tile_merge<UKM_OP_UNION, false, false, true, NTH, VT, false>(p, g, tid, s_keys, nullptr, nullptr, ok, ot, mask, amask, mmask, false,
+                                                                 ia0, ib0, nullptr, tbm, need);
+    const u32 dmask = amask & ~mmask;
+    PH(2);
+    // The block scan of setop_tile_kernel with the match count riding in the upper half of the union's word; the
+    // difference's count, where it is asked for, in a scan of its own behind the same barrier.  The
+    // MATCH count is what the tile publishes, behind the first barrier; an interior tile's order check runs after that.
+    u32 utot, mtot, dtot = 0, uexcl, mexcl, dexcl = 0, strad = 0;
+    {
+        const u32 v = (WU ? (u32)__popc(mask) : 0u) | ((u32)__popc(mmask) << 16);
+        const u32 vd = (u32)__popc(dmask);
+        const int lane = lane_id(), wave = tid >> 6;
+        const u32 incl = wave_incl_scan_u32(v);
+        u32 incl_d = 0;
+        if (WD) incl_d = wave_incl_scan_u32(vd);
+        if (lane == 63) {
+            s_scan[wave] = incl;
+            if (WD) s_scan_d[wave] = incl_d;
+        }
+        __syncthreads();
+        u32 wbase = 0, tot = 0, wbase_d = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const u32 t = s_scan[w];
+            if (w < wave) wbase += t;
+            tot += t;
+            if (WD) {
+                const u32 td = s_scan_d[w];
+                if (w < wave) wbase_d += td;
+                dtot += td;
+            }
+        }
+        const u32 excl = wbase + incl - v;
+        utot = tot & 0xFFFFu;
+        mtot = tot >> 16;
+        uexcl = excl & 0xFFFFu;
+        mexcl = excl >> 16;
+        if (WD) dexcl = wbase_d + incl_d - vd;
+        if (tid == 0) lb_publish(p.status, tile, (u64)mtot);
+        // s_t: a matched pair straddles the tile's front boundary (A[a0 - 1] == B[b0]; B[b0] is the next-B halo of a tile
+        // without B records) -- read by the look-back's wave before the image goes
+        if (WU && tid < 64) {
+            const bool pair = g.has_prev_a && (g.nb_t > 0 || g.has_next_b);
+            strad = (pair && s_keys[g.base_a - 1] == s_keys[g.base_b]) ? 1u : 0u;
+        }
+        if (fast) bad |= tile_check_order_lds<NTH, VT>(g, tid, s_keys);
+        __syncthreads();  // every thread has finished reading the tile from LDS
+    }
+    if (WU) tile_compact<false, VT>(uexcl, mask, ok, ot, s_keys, nullptr);
+    PH(3);
+    if (tid < 64) {
+        bool timed_out = false;
+        const u64 mp = lb_resolve(p.status, tile, (u64)mtot, lane_id(), TICKET ? nullptr : &timed_out);
+        if (tid == 0) {
+            // (disordered inputs can count more matches than A records: the flag voids the outputs, the clamp keeps the
+            //  offsets below inside [0, d_t + 1] whatever was counted)
+            s_misc[1] = mp < g.a0 ? mp : g.a0;
+            s_misc[2] = strad;
+        }
+        if (timed_out) bad |= FLAG_TIMEOUT;
+    }
+    PH(4);
+    {
+        u32 wbad = 0;
+#pragma unroll
+        for (u32 f = 1; f <= FLAG_TIMEOUT; f <<= 1)
+            if (__ballot((bad & f) != 0)) wbad |= f;
+        if (wbad && lane_id() == 0) atomicOr((unsigned long long *)&p.result[1], (unsigned long long)wbad);
+    }
+    __syncthreads();
+    const u64 m0 = s_misc[1];
+    if (WU) {
+        SetopArgs pu = p;
+        pu.out = mo.out[UKM_OP_UNION];
+        pu.out_cap = mo.cap[UKM_OP_UNION];
+        tile_flush<false, NTH>(pu, tid, setop_offset_of(UKM_OP_UNION, m0, g.a0, tile * (u64)TILE, s_misc[2]), utot, s_keys, nullptr);
+        __syncthreads();  // the union's survivors have left the image
+    }
+    const u32 dfrom = WI ? mtot : 0u;  // the difference's survivors lie behind the intersection's
+    if (WI) tile_compact<false, VT>(mexcl, mmask, ok, ot, s_keys, nullptr);
+    if (WD) tile_compact<false, VT>(dfrom + dexcl, dmask, ok, ot, s_keys, nullptr);
+    __syncthreads();
+    if (WI) {
+        SetopArgs pi = p;
+        pi.out = mo.out[UKM_OP_INTER];
+        pi.out_cap = mo.cap[UKM_OP_INTER];
+        tile_flush<false, NTH>(pi, tid, setop_offset_of(UKM_OP_INTER, m0, g.a0, 0, 0), mtot, s_keys, nullptr);
+    }
+    if (WD) {
+        SetopArgs pd = p;
+        pd.out = mo.out[UKM_OP_DIFF];
+        pd.out_cap = mo.cap[UKM_OP_DIFF];
+        tile_flush<false, NTH>(pd, tid, setop_offset_of(UKM_OP_DIFF, m0, g.a0, 0, 0), dtot, s_keys + dfrom, nullptr);
+    }
+    if (tid == 0 && tile == p.ntiles - 1) p.result[0] = m0 + mtot;  // M: the host derives the three totals
+    PH(5);
+#ifdef UKM_PROFILE_PHASES
+    if (tid == 0 && p.dbg) {
+        for (int i = 0; i < 7; i++) p.dbg[blockIdx.x * 8 + i] = ph[i];
+        p.dbg[blockIdx.x * 8 + 7] = 1;
+    }
+#endif
+}
+
 // rank of each element inside its run of equal codes (multiset path)
 __global__ void rank_in_run_kernel(const u64 *k, u64 n, u32 *rank) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1633,7 +1794,116 @@ int run_setop_pass(ukm_ctx *c, int op, const u64 *a, const u32 *ta, const u32 *r
     return UKM_OK;
 }
 
+// ---- ukm_setop2_multi: the fused pass (setop_multi_tile_kernel) ----
+#ifndef SETOP_VT_MULTI
+#define SETOP_VT_MULTI SETOP_VT
+#endif
+constexpr int VT_MULTI = SETOP_VT_MULTI;  // items per thread of the fused kernel (its partition is its own: any tile size would do)
+
+template <int OPS>
+void launch_multi(const SetopArgs &p, const SetopMultiOut &mo, hipStream_t st, bool ticket) {
+    const dim3 grid((unsigned)p.ntiles), block(NTS);
+    if (ticket) hipLaunchKernelGGL((setop_multi_tile_kernel<OPS, true, NTS, VT_MULTI>), grid, block, 0, st, p, mo);
+    else hipLaunchKernelGGL((setop_multi_tile_kernel<OPS, false, NTS, VT_MULTI>), grid, block, 0, st, p, mo);
+}
+
+// One pass over plain codes that writes every operation of `ops` (1 << UKM_OP_x each, at least two).  result_host[0] = M,
+// the number of matched pairs, [1] = flags.  A partition table of its own in the arena: the context's partition cache is
+// neither read nor written, so the passes around this one find it as they left it.
+int run_setop_multi_pass(ukm_ctx *c, u32 ops, const u64 *a, u64 na, const u64 *b, u64 nb, u64 *const out[3], const u64 out_cap[3],
+                         u64 result_host[2]) {
+    const u64 tile_items = (u64)NTS * VT_MULTI;
+    SetopArgs p = setop_args(c, a, nullptr, nullptr, na, b, nullptr, nullptr, nb, tile_items, 0u, nullptr, nullptr, 0, 0u, 0u);
+    if (p.ntiles > 0xFFFFFFFFull) UKM_FAIL(UKM_ERR_INVALID, "setop: input too large");
+    SetopMultiOut mo;
+    for (int x = 0; x < 3; x++) {
+        const bool want = ((ops >> x) & 1u) != 0;
+        mo.out[x] = want ? out[x] : nullptr;
+        mo.cap[x] = want ? out_cap[x] : 0;
+    }
+    LbCtl blk;  // the partition points behind it
+    UKM_TRY(ukm_lb_ctl_alloc(c, p.ntiles, p.ntiles + 1, &blk));
+    p.result = blk.result;
+    p.ticket = blk.ticket;
+    p.status = blk.status;
+    p.mp = blk.tail;
+#ifdef UKM_PROFILE_PHASES
+    UKM_TRY(ws_alloc_t(c, (size_t)p.ntiles * 8, &p.dbg));
+    UKM_HIP(hipMemsetAsync(p.dbg, 0, (size_t)p.ntiles * 8 * sizeof(u64), c->stream));
+#endif
+    const bool fused = p.ntiles >= 4 * PART_COARSE;  // (the fused kernel also zeroes the control block for the first attempt)
+    UKM_TRY(launch_partition(c, p, tile_items, false, fused ? PartKernels::FUSED : PartKernels::SINGLE));
+    const LbLaunch how = {"setop_multi", "fused set-op kernel", FLAG_TIMEOUT, true, false, fused};
+    UKM_TRY(ukm_lb_launch(c, blk, how, [&](bool ticket) {
+        if (ops == 3u) launch_multi<3>(p, mo, c->stream, ticket);
+        else if (ops == 5u) launch_multi<5>(p, mo, c->stream, ticket);
+        else if (ops == 6u) launch_multi<6>(p, mo, c->stream, ticket);
+        else launch_multi<7>(p, mo, c->stream, ticket);
+        return UKM_OK;
+    }, result_host));
+#ifdef UKM_PROFILE_PHASES
+    {
+        std::vector<u64> h((size_t)p.ntiles * 8);
+        UKM_HIP(hipMemcpy(h.data(), p.dbg, h.size() * sizeof(u64), hipMemcpyDeviceToHost));
+        double sum[8] = {0};
+        for (u64 t = 0; t < p.ntiles; t++) for (int i = 0; i < 8; i++) sum[i] += (double)h[(size_t)t * 8 + i];
+        double tot = 0; for (int i = 0; i < 7; i++) tot += sum[i];
+        fprintf(stderr, "[phases multi ops=%u tiles=%llu] cycles per tile:", ops, (unsigned long long)p.ntiles);
+        for (int i = 0; i < 7; i++) fprintf(stderr, " p%d=%.0f", i, sum[i] / sum[7]);
+        fprintf(stderr, " total=%.0f\n", tot / sum[7]);
+    }
+#endif
+    return UKM_OK;
+}
+
 }  // namespace
+
+// Two or three operations of one pair.  ops: 1 << UKM_OP_x each; the arrays are indexed by UKM_OP_x and only the
+// requested entries are touched.  Plain codes and at least two operations: one fused pass; everything else -- taxids of
+// either kind, one operation, duplicate codes inside an input -- one ukm_dev_setop2_ct per operation (the split route).
+int ukm_dev_setop2_multi(ukm_ctx *c, u32 ops, const u64 *a, const u32 *ta, u32 cta, u64 na, const u64 *b, const u32 *tb, u32 ctb,
+                         u64 nb, u32 flags, u64 *const out[3], u32 *const tout[3], const u64 out_cap[3], u64 n_out[3]) {
+    if (ops == 0 || ops >= 8u) UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2_multi: ops %u names no operation or an unknown one", ops);
+    if (ta) cta = 0;
+    if (tb) ctb = 0;
+    const bool tax = ta != nullptr || tb != nullptr || cta != 0 || ctb != 0;
+    const bool part_cache = (flags & UKM_F_INTERNAL_PART_CACHE) != 0;
+    flags &= ~UKM_F_INTERNAL_PART_CACHE;
+    if (!tax && (ops & (ops - 1)) != 0 && na + nb > 0) {
+        if (na + nb >= (1ull << 61)) UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2_multi: input too large");
+        u64 res[2] = {0, 0};
+        UKM_TRY(run_setop_multi_pass(c, ops, a, na, b, nb, out, out_cap, res));
+        if (res[1] & FLAG_UNSORTED) UKM_FAIL(UKM_ERR_UNSORTED, "ukm_setop2_multi: an input stream is not sorted");
+        if (!(res[1] & FLAG_DUP)) {
+            const u64 m = res[0];
+            const u64 total[3] = {na + nb - m, m, na - m};
+            bool fits = true;
+            for (int x = 0; x < 3; x++) {
+                if (!((ops >> x) & 1u)) continue;
+                n_out[x] = total[x];
+                if (total[x] > out_cap[x]) fits = false;
+            }
+            c->stat_setop_multi_fused++;
+            if (!fits) UKM_FAIL(UKM_ERR_CAPACITY, "ukm_setop2_multi: an output needs more records than its capacity");
+            // (a caller that wants taxids of streams that carry none: such records have taxid 0, as in ukm_dev_setop2_ct)
+            for (int x = 0; x < 3; x++)
+                if (((ops >> x) & 1u) && tout[x] && total[x]) UKM_HIP(hipMemsetAsync(tout[x], 0, total[x] * sizeof(u32), c->stream));
+            return UKM_OK;
+        }
+        // multiset inputs: the rank re-run and the unique fold stay where they are
+    }
+    c->stat_setop_multi_split++;
+    int rc = UKM_OK;
+    for (int x = 0; x < 3; x++) {
+        if (!((ops >> x) & 1u)) continue;
+        // (every operation runs, so that every n_out holds the size needed when one of them does not fit)
+        const int r = ukm_dev_setop2_ct(c, x, a, ta, cta, na, b, tb, ctb, nb, flags | (part_cache ? UKM_F_INTERNAL_PART_CACHE : 0u), out[x],
+                                        tout[x], out_cap[x], &n_out[x]);
+        if (r == UKM_ERR_CAPACITY) rc = r;
+        else UKM_TRY(r);
+    }
+    return rc;
+}
 
 // internal entry: all pointers are device pointers
 // One link of a chained fold: A's size is *na_dev (<= na_max), nothing is read back.  `ctl` = 8 zeroed words
@@ -1802,6 +2072,54 @@ extern "C" int ukm_setop2(ukm_ctx *ctx, int op, const uint64_t *a_keys, const ui
                           uint64_t nb, uint32_t flags, uint64_t *out_keys, uint32_t *out_taxids,
                           uint64_t out_cap, uint64_t *n_out) {
     return ukm_setop2_ft(ctx, op, a_keys, a_taxids, 0u, na, b_keys, b_taxids, 0u, nb, flags, out_keys, out_taxids, out_cap, n_out);
+}
+
+extern "C" int ukm_setop2_multi(ukm_ctx *ctx, uint32_t ops, const uint64_t *a_keys, const uint32_t *a_taxids, uint32_t a_file_taxid,
+                                uint64_t na, const uint64_t *b_keys, const uint32_t *b_taxids, uint32_t b_file_taxid, uint64_t nb,
+                                uint32_t flags, uint64_t *const out_keys[3], uint32_t *const out_taxids[3], const uint64_t out_cap[3],
+                                uint64_t n_out[3]) {
+    if (!ctx || !n_out || !out_keys || !out_cap || (!a_keys && na) || (!b_keys && nb))
+        UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2_multi: NULL argument");
+    if (ops == 0 || ops >= 8u) UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2_multi: ops %u names no operation or an unknown one", ops);
+    for (int x = 0; x < 3; x++)
+        if (((ops >> x) & 1u) && !out_keys[x] && out_cap[x]) UKM_FAIL(UKM_ERR_INVALID, "ukm_setop2_multi: NULL argument");
+    CallScope s;
+    UKM_TRY(ukm_begin(ctx, &s));
+    int rc = [&]() -> int {
+        const u64 *a = nullptr, *b = nullptr;
+        const u32 *ta = nullptr, *tb = nullptr;
+        u64 *out[3] = {nullptr, nullptr, nullptr};
+        u32 *tout[3] = {nullptr, nullptr, nullptr};
+        u64 cap[3] = {0, 0, 0};
+        UKM_TRY(ukm_in_t(ctx, a_keys, na, &a));
+        UKM_TRY(ukm_in_t(ctx, b_keys, nb, &b));
+        UKM_TRY(ukm_in_t(ctx, a_taxids, na, &ta));
+        UKM_TRY(ukm_in_t(ctx, b_taxids, nb, &tb));
+        const bool tax_in = a_taxids || b_taxids || a_file_taxid || b_file_taxid;
+        for (int x = 0; x < 3; x++) {  // (entries of operations that were not requested are never looked at)
+            if (!((ops >> x) & 1u)) continue;
+            cap[x] = out_cap[x];
+            uint32_t *const ht = out_taxids ? out_taxids[x] : nullptr;
+            UKM_TRY(ukm_out_query_t(ctx, out_keys[x], cap[x], &out[x]));
+            if (tax_in) UKM_TRY(ukm_out_query_t(ctx, ht, cap[x], &tout[x]));
+            else UKM_TRY(ukm_out_t(ctx, ht, cap[x], &tout[x]));
+        }
+        const u32 cta = ta ? 0u : a_file_taxid, ctb = tb ? 0u : b_file_taxid;
+        // (the split route's passes may use the partition cache exactly where ukm_setop2_ft's may; the fused pass never does)
+        const u32 cacheable = (s.top && na && nb && a == a_keys && b == b_keys) ? UKM_F_INTERNAL_PART_CACHE : 0u;
+        u64 n[3] = {0, 0, 0};
+        const int r = ukm_dev_setop2_multi(ctx, ops, a, ta, cta, na, b, tb, ctb, nb, (flags & (UKM_F_MIX_TAXID | UKM_F_CMP_TAXID)) | cacheable,
+                                           out, tout, cap, n);
+        for (int x = 0; x < 3; x++) {
+            if (!((ops >> x) & 1u)) continue;
+            n_out[x] = n[x];
+            const u64 keep = (r == UKM_OK) ? n[x] : 0;
+            ukm_out_resize(ctx, out_keys[x], keep * sizeof(u64));
+            if (out_taxids && out_taxids[x]) ukm_out_resize(ctx, out_taxids[x], keep * sizeof(u32));
+        }
+        return r;
+    }();
+    return ukm_finish(&s, rc);
 }
 
 extern "C" int ukm_partition_points(ukm_ctx *ctx, const uint64_t *keys, uint64_t n,

@@ -53,6 +53,7 @@ SYMBOLS = [
     "ukm_deflate", "ukm_deflate_bound", "ukm_crc32_combine",
     "ukm_inflate", "ukm_inflate_bound",
     "ukm_fastx",
+    "ukm_setop2_multi",
 ]
 
 
@@ -223,6 +224,7 @@ def load():
     # per-FILE taxids (one value per stream: the .unik header's global taxid)
     L.ukm_merge_k_ft.argtypes = [vp, pvp, pvp, vp, pu64, i32, i32, i32, vp, vp, u64, pu64]
     L.ukm_setop2_ft.argtypes = [vp, i32, vp, vp, u32, u64, vp, vp, u32, u64, u32, vp, vp, u64, pu64]
+    L.ukm_setop2_multi.argtypes = [vp, u32, vp, vp, u32, u64, vp, vp, u32, u64, u32, pvp, pvp, pu64, pu64]
     for f in (L.ukm_union_ft, L.ukm_inter_ft):
         f.argtypes = [vp, pvp, pvp, vp, pu64, i32, u32, vp, vp, u64, pu64]
     L.ukm_diff_ft.argtypes = [vp, pvp, pvp, vp, pu64, i32, vp, u32, vp, vp, u64, pu64]
@@ -908,6 +910,51 @@ class Context:
         n = C.c_uint64()
         _check(self.L.ukm_setop2_ft(self.h, op, pa, pta, fa, na, pb, ptb, fb, nb, flags, po, pot, cap, C.byref(n)), n.value)
         return (out[: n.value], out_taxids[: n.value]) if tax else out[: n.value]
+
+    def setop2_multi(self, a, b, ops=(OP_UNION, OP_INTER), a_taxids=None, b_taxids=None, flags=0, out=None, out_taxids=None):
+        """Two or three operations of ONE pair from a single pass over a and b (ukm_setop2_multi): {op: result}, each
+        entry what setop2(op, a, b, ...) returns -- the trimmed output, or (out, out_taxids) where taxids are present.
+        ops: the operations wanted (OP_UNION / OP_INTER / OP_DIFF); plain codes and at least two of them run fused,
+        everything else one pass per operation.  out / out_taxids: dicts {op: caller-owned buffer}; an operation without
+        an entry gets a buffer of setop2's default size (na + nb for the union, na otherwise).  Too small:
+        CapacityError with .needed = {op: records} for every requested operation."""
+        ops = tuple(int(x) for x in ops)
+        mask = 0
+        for x in ops:
+            mask |= (1 << x) if x >= 0 else 0
+        pa, na, k1 = _ptr(a, np.uint64)
+        pb, nb, k2 = _ptr(b, np.uint64)
+        fa = int(a_taxids) if _is_file_taxid(a_taxids) else 0
+        fb = int(b_taxids) if _is_file_taxid(b_taxids) else 0
+        pta, _, k3 = _ptr(None if _is_file_taxid(a_taxids) else a_taxids, np.uint32)
+        ptb, _, k4 = _ptr(None if _is_file_taxid(b_taxids) else b_taxids, np.uint32)
+        tax = (a_taxids is not None and not (_is_file_taxid(a_taxids) and fa == 0)) or \
+              (b_taxids is not None and not (_is_file_taxid(b_taxids) and fb == 0))
+        out = dict(out or {})
+        out_taxids = dict(out_taxids or {})
+        po, pot, cap, n = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        keep = []
+        for x in ops:
+            if not 0 <= x <= OP_DIFF:
+                continue   # (the library refuses the mask)
+            bound = na + nb if x == OP_UNION else na
+            if out.get(x) is None:
+                out[x] = _empty_like_kind(a, bound, np.uint64)
+            if tax and out_taxids.get(x) is None:
+                out_taxids[x] = _empty_like_kind(a, bound, np.uint32)
+            p, c, ka = _ptr(out[x], np.uint64)
+            pt, _, kb = _ptr(out_taxids.get(x), np.uint32)
+            po[x], pot[x], cap[x] = p, pt, c
+            keep += [ka, kb]
+        rc = self.L.ukm_setop2_multi(self.h, mask, pa, pta, fa, na, pb, ptb, fb, nb, flags, po, pot, cap, n)
+        if rc == ERR_CAPACITY:
+            try:
+                _check(rc)
+            except CapacityError as e:
+                e.needed = {x: int(n[x]) for x in ops}
+                raise
+        _check(rc)
+        return {x: ((out[x][: n[x]], out_taxids[x][: n[x]]) if tax else out[x][: n[x]]) for x in ops}
 
     def stream_table(self, keys_list, taxids_list=None):
         """Prepared pointer / length tables of a set of streams, to be passed IN PLACE OF keys_list to union / inter / diff /
