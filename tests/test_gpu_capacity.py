@@ -29,9 +29,9 @@ SIGNED = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32, np.dtype
 U64, U32 = np.uint64, np.uint32
 
 # records per tile, from the kernels' sources
-TILE_SETOP = 512 * 19       # ukm_setops.hip: SETOP_NT x SETOP_VT (plain keys; one taxid per file on both sides)
-TILE_SETOP_TAX = 512 * 7    #                 SETOP_NT x SETOP_VT_TAX (per-record taxids)
-TILE_SETOP_RANK = 512 * 12  #                 SETOP_NT x VT_RANK (the multiset re-run)
+TILE_SETOP = 512 * 19       # ukm_setop_kernels.h: SETOP_NT x SETOP_VT (plain keys; one taxid per file on both sides)
+TILE_SETOP_TAX = 512 * 7    #                      SETOP_NT x SETOP_VT_TAX (per-record taxids)
+TILE_SETOP_RANK = 512 * 12  #                      SETOP_NT x VT_RANK (the multiset re-run)
 TILE_UNIQ = 512 * 16        # ukm_scan.hip: UNIQ_NT x UNIQ_VT (half of it for the chunk protocol)
 TILE_UNIQ_TAX = 512 * 12    #               UNIQ_NT x UNIQ_VT_TAX
 TILE_SELECT = 256 * 8       # ukm_select.hip: NT x VT

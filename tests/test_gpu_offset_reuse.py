@@ -1,4 +1,4 @@
-"""Tile offsets from the cached match counts (ukm_setops.hip: the TABLE instantiation of setop_tile_kernel; DESIGN.md
+"""Tile offsets from the cached match counts (ukm_setop_kernels.h: the TABLE instantiation of setop_tile_kernel; DESIGN.md
 sections 4.1 and 4.12).  A plain-key union / inter / diff that hits the partition cache while the slot's match counts MP
 are valid runs WITHOUT the look-back: its tiles' output offsets come from MP (inter MP[t], diff a_t - MP[t], union
 d_t - MP[t] + s_t), every tile checks its own count against its step of the table, and a pass that finds a difference

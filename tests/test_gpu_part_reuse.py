@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 U64, U32 = np.uint64, np.uint32
 SEED = 0x70617274
 N = 1_500_000
-TILE = 512 * 19             # ukm_setops.hip: SETOP_NT x SETOP_VT
+TILE = 512 * 19             # ukm_setop_kernels.h: SETOP_NT x SETOP_VT
 MIN_TILES = 4 * 64          # 4 * PART_COARSE
 OP_UNION, OP_INTER, OP_DIFF = 0, 1, 2
 BASE = U64(1) << U64(32)    # every code lies above 2^32: room for a whole set BELOW the other one

@@ -21,7 +21,7 @@ UID = (OP_UNION, OP_INTER, OP_DIFF)
 COMBOS = {"UI": (OP_UNION, OP_INTER), "UD": (OP_UNION, OP_DIFF), "ID": (OP_INTER, OP_DIFF), "UID": UID}
 G64 = 0xA5A5A5A5A5A5A5A5
 GUARD = 64
-PART_COARSE = 64                 # ukm_setops.hip: the partition runs in two levels (one fused launch) from 4 x 64 tiles
+PART_COARSE = 64                 # ukm_setop_part.h: the partition runs in two levels (one fused launch) from 4 x 64 tiles
 CACHE_STATS = ("setop_part_hits", "setop_part_stale", "setop_offs_hits", "setop_offs_stale")
 
 

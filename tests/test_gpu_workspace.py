@@ -33,7 +33,7 @@ from test_gpu_capacity import (CASES, NAMES, TILED, Case, attempt, SEED, U32, U6
                                _big_merge, _stable, _o2, _kt)
 
 # ---- constants of the sources -----------------------------------------------------------------------------------------------
-PART_COARSE = 64                    # ukm_setops.hip: SETOP_PART_COARSE; two-level partition from 4 x PART_COARSE tiles
+PART_COARSE = 64                    # ukm_setop_part.h: SETOP_PART_COARSE; two-level partition from 4 x PART_COARSE tiles
 TWO_LEVEL_TILES = 4 * PART_COARSE
 SORT_LOCAL_MIN = 1 << 23            # ukm_sort.hip: the bucket route from this n (key_bits >= 32, option sort_local not 0)
 SORT_FUSED_MIN = 1 << 24            #               the fused-histogram general route from this n; below: host histograms

@@ -74,7 +74,9 @@ def test_merge_path_twin_on_a_known_case():
 
 
 def test_tile_constant_matches_the_source():
-    src = open(os.path.join(ROOT, "unikmer_amd", "csrc", "ukm_setops.hip")).read()
+    # the set-op translation unit: the source and the three headers it is split into (ukm_setops.hip's header comment)
+    src = "".join(open(os.path.join(ROOT, "unikmer_amd", "csrc", f)).read()
+                  for f in ("ukm_setop_part.h", "ukm_setop_tile.h", "ukm_setop_kernels.h", "ukm_setops.hip"))
     defs = dict(re.findall(r"^#define (SETOP_NT|SETOP_VT|SETOP_VT_MULTI) (\w+)", src, flags=re.M))
     nt = int(defs["SETOP_NT"])
     vt = defs["SETOP_VT_MULTI"]

@@ -181,7 +181,7 @@ struct ukm_ctx {
     // every call) and the next call on the same key VERIFIES it against the inputs as they are now instead of searching
     // again.  buf[0] = the verification's stale word (zero whenever `valid`), buf[PC_HEAD ...] = the table.
     // Behind the table's ntiles + 1 words a second column of ntiles + 1: MP[t] = how many matched pairs of (A, B) have their A
-    // record in front of boundary t.  Every plain-key operation's tile offsets follow from it (ukm_setops.hip:
+    // record in front of boundary t.  Every plain-key operation's tile offsets follow from it (ukm_setop_part.h:
     // setop_partition_verify_kernel), so a pass that finds it valid runs without the look-back.  Same key, same slot: it is
     // dropped wherever the table is; `counts_valid` is set only behind a pass that came back without any flag.
     struct PartCache {
