@@ -13,7 +13,8 @@ Tile sizes (records per workgroup), from the sources:
   ukm_setops.hip   (ukm_setop_kernels.h) 512 x 19 = 9728 plain, 512 x 7 = 3584 with per-record taxids (SETOP_VT_TAX), 512 x 12 = 6144 with
                    ranks and for diff without -t; the fused partition and its cache start at 4 * PART_COARSE = 256 tiles
   ukm_scan.hip     unique: 512 x 16 = 8192, 512 x 12 = 6144 with taxids, half of either in the chunk protocol
-  ukm_encode.hip   window kernel 2048 positions, minimizer 2048 windows, ntHash strip filter 256 lanes x L = 256 positions
+  ukm_encode.hip   (ukm_win_kernels.h, ukm_win_minimizer.h) window kernel 2048 positions, minimizer 2048 windows, ntHash strip
+                   filter 256 lanes x L = 256 positions
   ukm_select.hip, ukm_tsplit.hip, ukm_map.hip   256 x 8 = 2048
 Every shape below has at least 3 tiles and a partial last one.
 """

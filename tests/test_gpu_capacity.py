@@ -35,7 +35,7 @@ TILE_SETOP_RANK = 512 * 12  #                      SETOP_NT x VT_RANK (the multi
 TILE_UNIQ = 512 * 16        # ukm_scan.hip: UNIQ_NT x UNIQ_VT (half of it for the chunk protocol)
 TILE_UNIQ_TAX = 512 * 12    #               UNIQ_NT x UNIQ_VT_TAX
 TILE_SELECT = 256 * 8       # ukm_select.hip: NT x VT
-TILE_WIN = 2048             # ukm_encode.hip: ENC_WT windows per tile; MIN_MT of the minimizer kernel is the same
+TILE_WIN = 2048             # ukm_win_common.h: ENC_WT windows per tile; MIN_MT of the minimizer kernel is the same
 
 ROUTE_NONE, ROUTE_TREE, ROUTE_KWAY, ROUTE_PUNION, ROUTE_SRMERGE, ROUTE_SRCOMMON, ROUTE_PCOMMON, ROUTE_PLACE = range(8)
 PLAIN, UNIQUE, REPEATED, REPEATED_CHUNK, SINGLETON = 0, 1, 2, 3, 4

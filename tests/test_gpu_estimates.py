@@ -33,7 +33,7 @@ SLACK = 1 << 20
 
 
 def count_window_estimate(bases, max_hash):
-    """the estimate this input is built to defeat: ukm_count's window buffer (ukm_encode.hip)"""
+    """the estimate this input is built to defeat: ukm_count's window buffer (ukm_encode.hip: count_window_estimate)"""
     return 1.5 * (2.0 * max_hash / 2.0 ** 64) * bases + SLACK
 
 

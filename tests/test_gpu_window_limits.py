@@ -1,4 +1,4 @@
-"""The window kernels of csrc/ukm_encode.hip on both sides of each of their fixed-size LDS tables.
+"""The window kernels of csrc/ukm_win_kernels.h and csrc/ukm_win_minimizer.h on both sides of each of their fixed-size LDS tables.
 
 Three kernels keep a table of fixed size and hand the call to another path when an input does not fit it:
   * stripwin_kernel      SW_REC records under one tile of SW_NT x L positions   -> ENC_FLAG_OVERFLOW, window_kernel answers
@@ -25,14 +25,17 @@ ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 
 
 # ------------------------------------------------------------------------------------------ the limits, from the source
-with open(os.path.join(ROOT, "unikmer_amd", "csrc", "ukm_encode.hip")) as _fh:
-    _SRC = _fh.read()
+# (the window translation unit: the three headers with the device code and the source with the policies, as one text)
+_SRC = ""
+for _f in ("ukm_win_common.h", "ukm_win_kernels.h", "ukm_win_minimizer.h", "ukm_encode.hip"):
+    with open(os.path.join(ROOT, "unikmer_amd", "csrc", _f)) as _fh:
+        _SRC += _fh.read()
 
 
 def _src_ints(pattern):
     m = re.findall(pattern, _SRC, flags=re.M)
     if len(m) != 1:
-        raise RuntimeError("ukm_encode.hip: %d matches for %r: the limits this file stands on have moved" % (len(m), pattern))
+        raise RuntimeError("ukm_encode.hip and its headers: %d matches for %r: the limits this file stands on have moved" % (len(m), pattern))
     return tuple(int(x) for x in (m[0] if isinstance(m[0], tuple) else (m[0],)))
 
 
@@ -45,7 +48,7 @@ SW_REC, = _src_ints(r"^constexpr int SW_REC = (\d+);")
 ST_NT, = _src_ints(r"^constexpr int ST_NT = (\d+);")
 ST_CAP, = _src_ints(r"^#define ST_CAP_N (\d+)$")
 if len(re.findall(r"^constexpr int ST_CAP = ST_CAP_N;", _SRC, flags=re.M)) != 1:   # (the list has ST_CAP_N entries)
-    raise RuntimeError("ukm_encode.hip: ST_CAP is no longer ST_CAP_N")
+    raise RuntimeError("ukm_win_kernels.h: ST_CAP is no longer ST_CAP_N")
 SW_L_K32, SW_L_K64 = _src_ints(r"int L = \(k <= 32\) \? (\d+) : (\d+);")  # stripwin_kernel's default strip lengths
 ST_L_MAX, = _src_ints(r"L = std::min\((\d+), std::max\(64, atoi\(le\) / 64 \* 64\)\);")  # largest strip_l of the filter
 

@@ -4,7 +4,7 @@
 //   * ukm_map: the successive regions covered by k-mers of a set (map.go:116-491 at -x 0 -X 0: a region is a maximal run of
 //     windows whose code is in the set and, without -M, occurs once among the windows of its genome).
 //
-// Both are a JOIN of the genome's windows (run_windows, ukm_encode.hip) against a sorted code array, done in genome order:
+// Both are a JOIN of the genome's windows (run_windows, ukm_encode.hip; its kernels: ukm_win_kernels.h) against a sorted code array, done in genome order:
 //   join_kernel   every window looks its code up through a PREFIX DIRECTORY of the sorted array (ukm_dir.h; dir[p] = lower bound of
 //                 prefix p, 2^B + 1 words with B = log2(n) - 1: the bucket of a prefix holds 2-4 codes, one 128-byte line
 //                 most of the time) -- one directory read and one or two reads of the array per window instead of the
@@ -484,18 +484,9 @@ struct Windows {
 };
 int make_windows(ukm_ctx *c, const char *name, const u8 *bases, const u64 *rec_off, u64 n_rec, int k, int circular, int hashed,
                  Windows *W) {
-    UKM_TRY(ukm_in_t(c, rec_off, n_rec + 1, &W->rec_off));
-    u64 total_bases = 0, first = 0;
-    if (ukm_is_device_ptr(rec_off)) {
-        UKM_TRY(ukm_read_u64(c, W->rec_off + n_rec, &total_bases));
-        UKM_TRY(ukm_read_u64(c, W->rec_off, &first));
-    } else {
-        total_bases = rec_off[n_rec];
-        first = rec_off[0];
-    }
-    if (first != 0) UKM_FAIL(UKM_ERR_INVALID, "%s: rec_off[0] must be 0", name);
+    u64 total_bases = 0;
     const u8 *b = nullptr;
-    UKM_TRY(ukm_in_t(c, bases, total_bases, &b));
+    UKM_TRY(ukm_dev_stage_records(c, name, bases, rec_off, n_rec, &W->rec_off, &b, &total_bases));
     UKM_TRY(ws_alloc_t(c, (size_t)total_bases + 1, &W->w));
     UKM_TRY(ukm_dev_windows(c, hashed != 0, b, W->rec_off, n_rec, k, 1, circular, W->w, total_bases + 1, &W->n, total_bases, &W->win_off));
     if (W->n >= (1ull << 32))
