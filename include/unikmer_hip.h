@@ -684,6 +684,29 @@ int ukm_merge_k_ft(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *co
                    const uint64_t *lens, int nstreams, int mode, int final_round, uint64_t *out_keys,
                    uint32_t *out_taxids, uint64_t out_cap, uint64_t *n_out);
 
+/* ---- all-pairs shared code counts of many sets (new: the reference needs N(N-1)/2 runs of `inter | num` for this): what
+ *      Jaccard index, containment and Mash distance of 1000 sketches or .unik files are computed from, in one call.
+ *      out_counts[i * nstreams + j], i < nrows, j < nstreams: the number of DISTINCT codes that occur in both stream i and
+ *      stream j.  out_sizes[j], j < nstreams (may be NULL): the number of distinct codes of stream j (== out_counts[j][j]
+ *      where j < nrows).
+ *      keys[i]: host or device arrays, mixed freely; they need not be sorted or duplicate-free (a code that repeats inside a
+ *      stream counts once), and empty streams give a row and a column of zeros.  1 <= nrows <= nstreams: nrows == nstreams is
+ *      the full symmetric matrix, nrows < nstreams the first nrows streams (queries) against all.  1 <= nstreams <= 65536;
+ *      flags must be 0; anything else: UKM_ERR_INVALID.  out_counts / out_sizes: host or device; exactly nrows * nstreams
+ *      and nstreams items are written.  The result is a pure function of the inputs; counts are 64-bit end to end; running
+ *      out of device memory is UKM_ERR_NOMEM.
+ *      How: the (code, stream) records of all streams are sorted by code, a distinct code's rank is its column, and the
+ *      columns are walked in blocks; per block a bit matrix [stream][column] is set and pair_popc_kernel adds
+ *      popcount(row i AND row j) to the counts -- a cost that does not depend on how much the sets overlap.
+ *      ukm_last_kernel_ms: the summed time of the pair kernel's launches; ukm_last_call_ms: the whole call.
+ *      Statistics (ukm_ctx_get_stat), of the last call: "pair_columns" = distinct codes over all streams, "pair_blocks" =
+ *      column blocks walked, "pair_sort_us" / "pair_bits_us" / "pair_kernel_us" = device time in microseconds of the sort
+ *      and ranking step, of zeroing and setting the bits, and of the pair kernel.  Option "pair_block_cols" (developer and
+ *      test knob): columns per block, rounded up to whole K tiles of 2048; unset: the widest block whose bit matrix stays
+ *      within 1 GiB.  Results never depend on it. */
+int ukm_pair_counts(ukm_ctx *ctx, const uint64_t *const *keys, const uint64_t *lens, int nstreams, int nrows,
+                    uint32_t flags, uint64_t *out_counts, uint64_t *out_sizes);
+
 /* ---- multi-GPU helper: split points of a sorted stream for prefix sharding (SURVEY.md
  *      §8(e)): cuts[g] = lower_bound(keys, splitters[g]) for g in [0, n_split). */
 int ukm_partition_points(ukm_ctx *ctx, const uint64_t *keys, uint64_t n,

@@ -40,7 +40,7 @@ static const char *const UKM_OPTION_KEYS[] = {
     "sort_local", "sort_counting", "sort_fan", "win_strip", "nthash_strip", "force_ticket", "setop_src", "setop_defer", "punion_clade", "srmerge_clade", "map_sorted", "grep_lds",
     // tuning / diagnostics (developer)
     "punion_k0", "punion_claim", "punion_debug", "kway_k", "kway_r", "kway_top2", "kway_debug", "srmerge_fill", "srmerge_spr", "srmerge_buckets",
-    "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_part_reuse", "setop_offs_reuse", "setop_offs_ops", "setop_fix", "map_dir_slack",
+    "srmerge_debug", "fold_debug", "sort_debug", "strip_l", "win_strip_l", "setop_fused_part", "setop_part_reuse", "setop_offs_reuse", "setop_offs_ops", "setop_fix", "map_dir_slack", "pair_block_cols",
     // test aid: the byte every arena block is filled with before a top-level call (see ws_poison_fill)
     "ws_poison",
 };
@@ -114,6 +114,11 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "setop_offs_stale") == 0) *value = c->stat_setop_offs_stale;
     else if (strcmp(key, "setop_multi_fused") == 0) *value = c->stat_setop_multi_fused;
     else if (strcmp(key, "setop_multi_split") == 0) *value = c->stat_setop_multi_split;
+    else if (strcmp(key, "pair_columns") == 0) *value = c->stat_pair_columns;
+    else if (strcmp(key, "pair_blocks") == 0) *value = c->stat_pair_blocks;
+    else if (strcmp(key, "pair_sort_us") == 0) *value = c->stat_pair_sort_us;
+    else if (strcmp(key, "pair_bits_us") == 0) *value = c->stat_pair_bits_us;
+    else if (strcmp(key, "pair_kernel_us") == 0) *value = c->stat_pair_kernel_us;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "window_route") == 0) *value = c->stat_window_route;
     else if (strcmp(key, "window_strip_declined") == 0) *value = c->stat_window_strip_declined;
@@ -430,6 +435,7 @@ int ukm_begin(ukm_ctx *c, CallScope *s) {
         (void)hipEventRecord(c->ev_start, c->stream);
         c->ev_valid = false;
         c->evk_valid = false;
+        c->kernel_ms_sum_valid = false;
     }
     s->mark = ws_mark(c);
     return UKM_OK;
@@ -537,6 +543,10 @@ extern "C" int ukm_last_route(ukm_ctx *c) { return c ? c->last_route : 0; }
 
 extern "C" int ukm_last_kernel_ms(ukm_ctx *c, float *ms) {
     if (!c || !ms) UKM_FAIL(UKM_ERR_INVALID, "ukm_last_kernel_ms: NULL argument");
+    if (c->kernel_ms_sum_valid) {  // several launches, already summed (ukm_pair_counts)
+        *ms = c->kernel_ms_sum;
+        return UKM_OK;
+    }
     if (!c->evk_valid) return ukm_last_call_ms(c, ms);
     UKM_HIP(hipEventSynchronize(c->ev_k1));
     UKM_HIP(hipEventElapsedTime(ms, c->ev_k0, c->ev_k1));

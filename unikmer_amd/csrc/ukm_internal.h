@@ -174,6 +174,14 @@ struct ukm_ctx {
     u64 stat_setop_offs_stale = 0;  // ... whose tiles counted otherwise (contents changed in place, partition intact): the pass ran again with the look-back
     u64 stat_setop_multi_fused = 0;  // ukm_setop2_multi calls answered by the one fused pass
     u64 stat_setop_multi_split = 0;  // ... by one ordinary pass per operation (taxids, one operation, duplicate codes)
+    // of the last ukm_pair_counts (ukm_pairs.hip): distinct codes over all streams, column blocks walked, and the device time,
+    // in microseconds, of its three steps: records sorted and ranked, bits set (zeroing included), pair kernel launches
+    u64 stat_pair_columns = 0, stat_pair_blocks = 0;
+    u64 stat_pair_sort_us = 0, stat_pair_bits_us = 0, stat_pair_kernel_us = 0;
+    // ukm_last_kernel_ms of a call whose dominant kernel ran as several launches: their summed time (kernel_ms_sum_valid;
+    // cleared when a top-level call begins), which one ev_k0 / ev_k1 bracket cannot hold
+    float kernel_ms_sum = 0.f;
+    bool kernel_ms_sum_valid = false;
 
     // Partition cache of the public 2-way set operation (ukm_setops.hip: run_setop_pass).  The merge-path table depends on
     // (A, B, |A|, |B|, tile size) only -- union, inter and diff of one pair share it -- so the context keeps the table of the

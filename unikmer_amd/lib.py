@@ -54,6 +54,7 @@ SYMBOLS = [
     "ukm_inflate", "ukm_inflate_bound",
     "ukm_fastx",
     "ukm_setop2_multi",
+    "ukm_pair_counts",
 ]
 
 
@@ -225,6 +226,7 @@ def load():
     L.ukm_merge_k_ft.argtypes = [vp, pvp, pvp, vp, pu64, i32, i32, i32, vp, vp, u64, pu64]
     L.ukm_setop2_ft.argtypes = [vp, i32, vp, vp, u32, u64, vp, vp, u32, u64, u32, vp, vp, u64, pu64]
     L.ukm_setop2_multi.argtypes = [vp, u32, vp, vp, u32, u64, vp, vp, u32, u64, u32, pvp, pvp, pu64, pu64]
+    L.ukm_pair_counts.argtypes = [vp, pvp, pu64, i32, i32, u32, vp, vp]
     for f in (L.ukm_union_ft, L.ukm_inter_ft):
         f.argtypes = [vp, pvp, pvp, vp, pu64, i32, u32, vp, vp, u64, pu64]
     L.ukm_diff_ft.argtypes = [vp, pvp, pvp, vp, pu64, i32, vp, u32, vp, vp, u64, pu64]
@@ -1067,6 +1069,29 @@ class Context:
     def merge_k(self, keys_list, taxids_list=None, mode=PLAIN, final_round=True, out=None, out_taxids=None):
         return self._nway("merge", keys_list, taxids_list, lambda t, f: 2 * t, (mode, final_round), 0, out,
                           out_taxids)
+
+    def pair_counts(self, keys_list, rows=None, out=None, sizes=True):
+        """All-pairs shared code counts (ukm_pair_counts): counts[i][j] = the number of distinct codes streams i and j share,
+        i < rows (default: all n streams, the full symmetric matrix), j < n; sizes[j] = the distinct codes of stream j.
+        keys_list: numpy arrays or torch tensors (host or device, mixed), as for union; they need not be sorted or
+        duplicate-free.  Returns (counts, sizes): counts a (rows, n) uint64 array on the host, or `out` (a contiguous array or
+        tensor of rows * n 8-byte items, host or device) as the caller gave it; sizes an (n,) uint64 host array, the array or
+        tensor passed as `sizes`, or None for sizes=False.  similarity.py turns the pair into Jaccard / containment / Mash."""
+        kp, _, lens, n, _, _, keep, _ = self._nway_args(list(keys_list), None)
+        rows = n if rows is None else int(rows)
+        if out is None and 1 <= rows <= n:
+            out = np.empty((rows, n), dtype=np.uint64)
+        if sizes is True:
+            sizes = np.empty(max(n, 1), dtype=np.uint64)[:n]
+        elif sizes is False:
+            sizes = None
+        po, cap, _ = _ptr(out, np.uint64)
+        ps, scap, _ = _ptr(sizes, np.uint64)
+        if 1 <= rows <= n:
+            assert cap == rows * n, "out holds %d items, the matrix has %d x %d" % (cap, rows, n)
+            assert sizes is None or scap == n, "sizes holds %d items for %d streams" % (scap, n)
+        _check(self.L.ukm_pair_counts(self.h, C.cast(kp, C.POINTER(C.c_void_p)), lens, n, rows, 0, po, ps))
+        return out, sizes
 
     def common_threshold(self, nfiles, proportion=1.0, number=0):
         return self.L.ukm_common_threshold(nfiles, proportion, number)
