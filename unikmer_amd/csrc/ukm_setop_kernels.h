@@ -179,9 +179,12 @@ __global__ void setop_ct_kernel(SetopArgs p, int op) {
 //   and the host re-runs with TICKET = true, where tile ids come from an atomic counter and
 //   forward progress holds for any dispatch order.
 // TABLE = true (plain keys, union / inter / diff): the tiles' output offsets are known before the launch (p.base, see
-//   setop_partition_verify_kernel).  Tile id = blockIdx.x, no ticket, nothing published, nobody waited for: the tiles are
-//   independent of each other.  A tile whose count differs from its step of the table raises FLAG_OFFS and stores no more
-//   than the step.
+//   setop_partition_verify_kernel).  No ticket, nothing published, nobody waited for: the tiles are independent of each
+//   other.  A tile whose count differs from its step of the table raises FLAG_OFFS and stores no more than the step.
+//   Tile id = ukm_setop_order::tile_of(blockIdx.x) when p.xcd_order is set: each XCD runs a range of consecutive tiles, so
+//   neighbouring tiles share an L2 (the lines their ranges begin and end in; mp[] and base[]).  ONLY this form may: under
+//   a look-back a chunk's first tile would wait for the last tile of the chunk in front of it, which starts a whole
+//   chunk of dispatches later -- every look-back form keeps blockIdx.x or tickets, and so does setop_multi_tile_kernel.
 // UKM_OP_MERGE_INTERNAL (ukm_internal.h): plain 2-way MERGE of two non-decreasing streams, every record
 //   kept (A first on ties).  Output size is known (|A| + |B|), so the tile kernel needs no look-back for it.
 // Up to 80 KB of LDS per workgroup (plain keys; taxids OR ranks riding along): two 512-thread workgroups per CU = 4
@@ -216,7 +219,7 @@ void setop_tile_kernel(SetopArgs p) {
     }
     PH_BEGIN();
     u64 tile;
-    if constexpr (TABLE) tile = blockIdx.x;
+    if constexpr (TABLE) tile = ukm_setop_order::tile_of(blockIdx.x, p.ntiles, p.xcd_order);  // (a block without a tile: >= p.ntiles)
     else tile = lb_tile_id<TICKET>(p.ticket, &s_misc[0]);
     PH(0);
     setop_resolve_sizes(p, (u64)TILE);
@@ -586,7 +589,7 @@ void launch_tile(const SetopArgs &p, hipStream_t st, bool ticket) {
 // the TABLE instantiations: plain keys, the three public operations
 template <int NTH, int VT>
 void launch_table(int op, const SetopArgs &p, hipStream_t st) {
-    const dim3 grid((unsigned)p.ntiles), block(NTH);
+    const dim3 grid((unsigned)ukm_setop_order::grid_of(p.ntiles, p.xcd_order)), block(NTH);
     if (op == UKM_OP_UNION) hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_UNION, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);
     else if (op == UKM_OP_INTER) hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_INTER, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((setop_tile_kernel<UKM_OP_DIFF, false, false, false, NTH, VT, false, false, true>), grid, block, 0, st, p);

@@ -24,6 +24,7 @@ struct SetopArgs {
     u64 ntiles;
     TaxDev tax;
     u32 flags;
+    u32 xcd_order;  // TABLE instantiation only: non-zero = block -> tile by ukm_setop_order.h, 0 = tile = block
     u64 *dbg;  // UKM_PROFILE_PHASES only
     // chained folds (ukm_inter / ukm_diff over many files): |A| is the previous call's result count and stays
     // on the device; na / ntiles above are then upper bounds used for the launch geometry only

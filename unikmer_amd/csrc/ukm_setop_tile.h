@@ -529,6 +529,12 @@ __device__ __forceinline__ void tile_compact(u32 excl, u32 mask, const u64 (&ok)
 
 // LDS -> HBM: contiguous coalesced run of `count` records at out[base ...), 16 bytes per store
 // where the global address allows it (the first/last record may go out alone).
+// SETOP_FLUSH_NT: the cache policy of the 16-byte stores of plain keys (with per-record taxids they are non-temporal
+// anyway, see tile_load).  0 = the default policy, 1 = nt.  An experiment switch like SETOP_DMA_NT, a compile-time
+// constant for the same reason; the measurements behind the default are in profiles/xcd_order_notes.md.
+#ifndef SETOP_FLUSH_NT
+#define SETOP_FLUSH_NT 0
+#endif
 template <bool TAX, int NTH>
 __device__ __forceinline__ void tile_flush(const SetopArgs &p, int tid, u64 base, u32 count, const u64 *s_keys,
                                            const u32 *s_tax) {
@@ -540,7 +546,7 @@ __device__ __forceinline__ void tile_flush(const SetopArgs &p, int tid, u64 base
             const int i0 = 2 * m - sh, i1 = i0 + 1;
             const bool v0 = i0 >= 0, v1 = i1 < (int)count;
             const u64 k0 = s_keys[v0 ? i0 : 0], k1 = s_keys[v1 ? i1 : 0];
-            if (TAX && v0 && v1) {  // (non-temporal beside the taxid look-ups: see tile_load)
+            if ((TAX || SETOP_FLUSH_NT) && v0 && v1) {  // (non-temporal beside the taxid look-ups: see tile_load)
                 typedef u64 v2u64 __attribute__((ext_vector_type(2)));
                 v2u64 w;
                 w.x = k0;

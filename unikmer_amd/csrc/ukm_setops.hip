@@ -42,6 +42,7 @@
 #include <algorithm>
 
 #include "ukm_device.h"
+#include "ukm_setop_order.h"
 
 namespace {
 
@@ -49,11 +50,23 @@ namespace {
 #include "ukm_setop_tile.h"
 #include "ukm_setop_kernels.h"
 
-// Operations that take their tile offsets from the cached match counts, 1 << op each (union 1, inter 2, diff 4).  The union
-// keeps the look-back: it writes 10.7 GB at 2 x 1e9 and its look-back waits hide behind the stores -- its TABLE kernel was
-// no faster than the spread between runs (profiles/offs_reuse_notes.md section 3), inter's is 0.4 ms faster.
+// Operations that take their tile offsets from the cached match counts whatever the size, 1 << op each (union 1, inter 2,
+// diff 4): inter's TABLE kernel is 0.4 ms faster than its look-back at 2 x 1e9 (profiles/offs_reuse_notes.md section 3).
+// The union's, with tile = block, tied with its look-back; with each XCD on consecutive tiles (below) it is 6 to 9 % faster
+// at every size measured, 2 x 1e7 to 2 x 1e9 (profiles/xcd_order_notes.md): the union takes the table from
+// SETOP_OFFS_UNION_MIN_TILES tiles, the smallest size measured, and keeps the look-back below.
 #ifndef SETOP_OFFS_OPS
 #define SETOP_OFFS_OPS 6
+#endif
+#ifndef SETOP_OFFS_UNION_MIN_TILES
+#define SETOP_OFFS_UNION_MIN_TILES 2048  /* 2 x 1e7 codes are 2056 tiles */
+#endif
+// The tile order of a TABLE pass, 1 << op each: set = each XCD runs a range of consecutive tiles (ukm_setop_order.h), clear
+// = tile = block.  The union gains 0.3 ms of 4.8 at 2 x 1e9; the intersection, which stores a third as much, LOSES 1 to
+// 4 % at every size (profiles/xcd_order_notes.md), and the difference is the intersection's shape.  UKM_SETOP_XCD_ORDER=0|1
+// (developer knob): no table pass / every table pass.
+#ifndef SETOP_XCD_ORDER
+#define SETOP_XCD_ORDER 1
 #endif
 
 // what a pass and a chained link (na = the bound, the link adds na_dev) hand to their kernels, less the control block
@@ -83,19 +96,22 @@ void bind_ctl(SetopArgs &p, const LbCtl &blk) {
 // The host side of -DUKM_PROFILE_PHASES (the kernels' side: PH_BEGIN / PH / PH_END in ukm_setop_kernels.h): eight words per
 // tile in front of the launches, and behind them one line on stderr, "[phases <label> tiles=N] cycles per tile: p0=.. ..
 // total=..".  Nothing in the product build.
+// (the words are indexed by BLOCK: a table pass in XCD order has up to ukm_setop_order::XCDS - 1 more blocks than tiles)
 int setop_phases_begin(ukm_ctx *c, SetopArgs &p) {
 #ifdef UKM_PROFILE_PHASES
-    UKM_TRY(ws_alloc_t(c, (size_t)p.ntiles * 8, &p.dbg));
-    UKM_HIP(hipMemsetAsync(p.dbg, 0, (size_t)p.ntiles * 8 * sizeof(u64), c->stream));
+    const size_t nblocks = (size_t)ukm_setop_order::grid_of(p.ntiles, 1);
+    UKM_TRY(ws_alloc_t(c, nblocks * 8, &p.dbg));
+    UKM_HIP(hipMemsetAsync(p.dbg, 0, nblocks * 8 * sizeof(u64), c->stream));
 #endif
     return UKM_OK;
 }
 int setop_phases_report(const SetopArgs &p, const char *label_fmt, int label_arg) {
 #ifdef UKM_PROFILE_PHASES
-    std::vector<u64> h((size_t)p.ntiles * 8);
+    const size_t nblocks = (size_t)ukm_setop_order::grid_of(p.ntiles, 1);
+    std::vector<u64> h(nblocks * 8);
     UKM_HIP(hipMemcpy(h.data(), p.dbg, h.size() * sizeof(u64), hipMemcpyDeviceToHost));
     double sum[8] = {0};
-    for (u64 t = 0; t < p.ntiles; t++) for (int i = 0; i < 8; i++) sum[i] += (double)h[(size_t)t * 8 + i];
+    for (size_t t = 0; t < nblocks; t++) for (int i = 0; i < 8; i++) sum[i] += (double)h[t * 8 + i];
     double tot = 0; for (int i = 0; i < 7; i++) tot += sum[i];
     fprintf(stderr, "[phases ");
     fprintf(stderr, label_fmt, label_arg);
@@ -191,7 +207,14 @@ void pass_open_cache(Pass &s, bool may_cache) {
         s.plan = Plan::VERIFY_LOOKBACK;
         if (slot.counts) {  // the column still belongs to the table this pass works on
             s.counts = Counts::KEPT;
-            if (s.offs_on && ((ukm_env_int(c, "UKM_SETOP_OFFS_OPS", SETOP_OFFS_OPS) >> s.op) & 1) != 0) s.plan = Plan::VERIFY_TABLE;
+            // the default: SETOP_OFFS_OPS, and the union from SETOP_OFFS_UNION_MIN_TILES tiles; the knob names the operations itself
+            const int large_union = p.ntiles >= SETOP_OFFS_UNION_MIN_TILES ? 1 << UKM_OP_UNION : 0;
+            if (s.offs_on && ((ukm_env_int(c, "UKM_SETOP_OFFS_OPS", SETOP_OFFS_OPS | large_union) >> s.op) & 1) != 0) s.plan = Plan::VERIFY_TABLE;
+            // the table pass's tile order (a grid of whole chunks that no longer fits 32 bits: tile = block)
+            const int xcd_knob = ukm_env_int(c, "UKM_SETOP_XCD_ORDER", -1);
+            const int xcd_ops = xcd_knob < 0 ? SETOP_XCD_ORDER : (xcd_knob ? 7 : 0);
+            if (s.plan == Plan::VERIFY_TABLE && ((xcd_ops >> s.op) & 1) != 0 && ukm_setop_order::grid_of(p.ntiles, 1) <= 0xFFFFFFFFull)
+                p.xcd_order = 1;
         }
     }
 }
