@@ -169,6 +169,13 @@ int ukm_last_route(ukm_ctx *ctx);
  *      "window_strip_declined" = launches of a strip kernel, over the context's life, that gave up -- more records under one
  *      tile than stripwin_kernel's table holds, more candidates in one tile than nthash_strip_kernel's list -- so that the
  *      general kernel answered the call (same result, one wasted launch),
+ *      "sort_route" = the route that completed the context's most recent outermost radix sort (ukm_sort_u64, ukm_sort_pairs
+ *      and the sort inside every call that sorts): 1 host histograms, 2 fused histograms, 3 top bits + LDS buckets, 4 chunks
+ *      of 2^31 records merged (the sorts of the chunks, and of the oversized buckets gathered by route 3, do not overwrite it),
+ *      "sort_bucket_declined" = times, over the context's life, route 3 was entered and handed the keys to the general passes
+ *      (narrow keys, a sample or the bucket sizes said "crowded"), "sort_oversized_buckets" = buckets beyond the largest size
+ *      class that the most recent outermost sort, if it took route 3, gathered and sorted by the general passes (0 when none; a
+ *      route-4 sort leaves it as it was: the sorts of its chunks do not write it),
  *      "punion_flags" = the flag word the most recent hash-probe pass of this context left (union, union of files with one
  *      taxid each, counting probes of `common`; 0 when none has run, and cleared when a call tries such a route, so that
  *      an attempt that declines in front of its pass shows 0 and not an earlier call's word): 1 PU_FLAG_UNSORTED a file is not sorted, 2

@@ -661,6 +661,8 @@ def test_beyond_2_30_and_2_32_records(env, monkeypatch):
         ctx.sort_u64(S, 62)
         assert _sorted_in_slices(S) and _xor(torch, S) == x0, knob
         assert torch.equal(S, ref), knob
+        # statistic "sort_route": 3 top bits + LDS buckets, 2 every pass through HBM with fused histograms
+        assert ctx.stat("sort_route") == (3 if knob is None else 2), (knob, ctx.stat("sort_route"))
         if knob is None:
             _sort_windows_match_oracle(torch, O, K, S)
         del S
@@ -711,6 +713,7 @@ def test_beyond_2_30_and_2_32_records(env, monkeypatch):
     S = K.clone()
     ctx.sort_u64(S, 62)
     assert _sorted_in_slices(S) and _xor(torch, S) == x0
+    assert ctx.stat("sort_route") == 4, ctx.stat("sort_route")      # chunks of 2^31 records, merged
     _sort_windows_match_oracle(torch, O, K, S)
     del K, S
     ctx.trim()

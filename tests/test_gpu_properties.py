@@ -366,7 +366,9 @@ def test_sort_top16_then_lds_buckets(env, monkeypatch):
     (ukm_sort.hip).  Against torch.sort and against the all-passes route (UKM_SORT_LOCAL=0): evenly spread 62-bit and
     64-bit keys (all buckets small), keys with a few heavy buckets (sorted by the general route afterwards), keys
     crowded into a handful of buckets (the whole call falls back), narrow keys handed over as 64-bit (the OR word narrows
-    them), duplicates, all-ones keys, every key the same."""
+    them), duplicates, all-ones keys, every key the same.  The pair sort of every case runs behind the loop over the
+    knob, with UKM_SORT_LOCAL=0 still set: this test covers pairs on the all-passes route only (pairs on the bucket route:
+    test_sort_three_top_passes_then_lds_buckets, test_gpu_workspace.py::test_sort)."""
     torch, bench, lib, ctx, A, B = env
     dev = A.device
     n = 20_000_000
@@ -402,7 +404,11 @@ def test_sort_top16_then_lds_buckets(env, monkeypatch):
     cases.append((rnd(62) & ~(((1 << 26) - 1) << 20), 62))
     z = rnd(62, n // 40).repeat(40)
     cases.append((z[torch.randperm(z.numel(), device=dev, generator=g)], 62))
-    for x, bits in cases:
+    # statistic "sort_route" on the default setting: 3 the bucket route, 2 the fused-histogram passes after the bucket route
+    # handed the call back (16 buckets; 62-bit keys that a few all-ones keys make 64 wide: a quarter of the buckets holds
+    # everything; one key: a single bucket does); under UKM_SORT_LOCAL=0 always 2
+    routes = (3, 3, 3, 2, 3, 2, 2, 3, 3)
+    for (x, bits), route in zip(cases, routes):
         exp = usort(x)
         for knob in (None, "0"):
             if knob is None:
@@ -410,19 +416,23 @@ def test_sort_top16_then_lds_buckets(env, monkeypatch):
             else:
                 monkeypatch.setenv("UKM_SORT_LOCAL", knob)
             w = x.clone()
+            declined = ctx.stat("sort_bucket_declined")
             ctx.sort_u64(w, bits)
             assert torch.equal(w, exp), (bits, knob)
+            assert ctx.stat("sort_route") == (route if knob is None else 2), (bits, knob, ctx.stat("sort_route"))
+            assert ctx.stat("sort_bucket_declined") == declined + (knob is None and route == 2), (bits, knob)
         # taxids riding along: the order of equal keys is the input order (stable)
         order = torch.sort(x ^ (-1 << 63), stable=True).indices
         w = x.clone()
         v = torch.arange(n, dtype=torch.int32, device=dev)
         ctx.sort_pairs(w, v, bits)
         assert torch.equal(w, exp) and torch.equal(v.long(), order), (bits, "pairs")
+        assert ctx.stat("sort_route") == 2, (bits, "pairs", ctx.stat("sort_route"))     # (UKM_SORT_LOCAL is still 0 here)
         del order, w, v
     monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
 
 
-def test_sort_three_top_passes_then_lds_buckets(env):
+def test_sort_three_top_passes_then_lds_buckets(env, monkeypatch):
     """Beyond 1.34e8 keys the bucket route sorts by the top 24 bits (three scatter passes, the result sits in the scratch
     copy) and the bucket kernels write the caller's array from there: 1.6e8 random 62-bit keys and 64-bit keys with
     duplicates against torch.sort, keys only and with taxids (stable)."""
@@ -445,10 +455,19 @@ def test_sort_three_top_passes_then_lds_buckets(env):
         exp, order = srt.values ^ (-1 << 63), srt.indices
         del srt
         w = x.clone()
+        monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
         ctx.sort_u64(w, bits)
         assert torch.equal(w, exp), bits
+        assert ctx.stat("sort_route") == 3, (bits, ctx.stat("sort_route"))      # the bucket route
+        monkeypatch.setenv("UKM_SORT_LOCAL", "0")
+        w.copy_(x)
+        ctx.sort_u64(w, bits)
+        assert torch.equal(w, exp), (bits, "0")
+        assert ctx.stat("sort_route") == 2, (bits, "0", ctx.stat("sort_route"))  # every pass through HBM: fused histograms
+        monkeypatch.delenv("UKM_SORT_LOCAL", raising=False)
         v = torch.arange(n, dtype=torch.int32, device=dev)
         w.copy_(x)
         ctx.sort_pairs(w, v, bits)
         assert torch.equal(w, exp) and torch.equal(v.long(), order), (bits, "pairs")
+        assert ctx.stat("sort_route") == 3, (bits, "pairs", ctx.stat("sort_route"))
         del w, v, exp, order, x

@@ -35,7 +35,7 @@ from test_gpu_capacity import (CASES, NAMES, TILED, Case, attempt, SEED, U32, U6
 # ---- constants of the sources -----------------------------------------------------------------------------------------------
 PART_COARSE = 64                    # ukm_setop_part.h: SETOP_PART_COARSE; two-level partition from 4 x PART_COARSE tiles
 TWO_LEVEL_TILES = 4 * PART_COARSE
-SORT_LOCAL_MIN = 1 << 23            # ukm_sort.hip: the bucket route from this n (key_bits >= 32, option sort_local not 0)
+SORT_LOCAL_MIN = 1 << 23            # ukm_sort_plan.h: the bucket route from this n (key_bits >= 32, option sort_local not 0)
 SORT_FUSED_MIN = 1 << 24            #               the fused-histogram general route from this n; below: host histograms
 LS_TOP_MIN, LS_BUCKET_AVG = 12, 1400  #             ls_plan: the smallest top-bit count with n >> topb <= 1400 (topb <= 16 here)
 LS_CLASS_MAX = 256 * 16             #               LS_NT x the largest LS_CLASS_KPT: a bucket beyond it is oversized
@@ -46,7 +46,7 @@ MB = 1 << 20
 
 
 def ls_topb(n):
-    """ls_plan of ukm_sort.hip for n < 2^27"""
+    """ls_plan of ukm_sort_plan.h for n < 2^27"""
     assert (n >> 16) <= 2048
     topb = LS_TOP_MIN
     while topb < 16 and (n >> topb) > LS_BUCKET_AVG:
@@ -295,7 +295,9 @@ def test_big_setop2(env, op, form, fused, ticket):
 
 
 # ---- 3b. ukm_sort_u64 / ukm_sort_pairs ---------------------------------------------------------------------------------------------
-LS_CLASS_KPT = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16)   # x LS_NT = 256 keys: the size classes of the bucket kernel
+LS_CLASS_KPT = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16)   # ukm_sort_plan.h; x LS_NT = 256 keys: the size classes of the bucket kernel
+LS_MIN_BITS = 8 * 2 + 16            #               two top passes + two digits for the buckets' own passes: narrower keys are declined
+ROUTE_HOST_HIST, ROUTE_FUSED, ROUTE_BUCKETS, ROUTE_CHUNKED = 1, 2, 3, 4   # enum SortRoute: the values of the statistic "sort_route"
 LS_FAN_MIN = 3                      #               size classes that must occur for the launches to fan out over the side streams
 SORT_ROWS = {   # name: (n, shape of the keys, options)
     "host-hist": (100_003, "even", {}),
@@ -307,12 +309,20 @@ SORT_ROWS = {   # name: (n, shape of the keys, options)
     "fan": (1 << 23, "sloped", {"sort_counting": 1}),        # buckets of every size up to twice the average: side streams
     "no-fan": (1 << 23, "sloped", {"sort_counting": 1, "sort_fan": 0}),   # the same classes on one stream
     "fused-hist": (1 << 24, "even", {"sort_local": 0}),
+    # keys narrower than declared: the OR word of the first histogram narrows them (key_bits = 64 only: a narrower
+    # declaration is taken at its word)
+    "narrow-64": (1 << 23, "even", {"sort_counting": 1}),    # 40 bits: still two top passes + two digits, the route goes on
+    "too-narrow-64": (1 << 23, "even", {}),                  # 30 bits: declined, and below SORT_FUSED_MIN the host histograms answer
+    "gives-up": (1 << 23, "16-buckets", {}),                 # every key in 16 buckets: the classify verdict hands the call back
 }
+SORT_WIDTH = {"narrow-64": 40, "too-narrow-64": 30}          # row: bits the keys really have (default: as declared)
+SORT_BITS = {"narrow-64": (64,), "too-narrow-64": (64,)}     # row: the declared widths it runs at (default: 62 and 64)
 CROWDED = ((5, 600_000), (77, 200_000))     # (bucket, keys): as test_sort_top16_then_lds_buckets, at n = 2^23
 
 
 def sort_input(row, bits, seed):
     n, shape, _ = SORT_ROWS[row]
+    bits = SORT_WIDTH.get(row, bits)
     rng = np.random.default_rng(seed)
     x = rng.integers(0, 1 << bits, n, dtype=U64)
     if shape == "sloped":                   # the density rises with the value: bucket b holds n (2 b + 1) / buckets^2 keys
@@ -324,26 +334,41 @@ def sort_input(row, bits, seed):
             x[at:at + count] = (x[at:at + count] & U64((1 << low) - 1)) | U64(bucket << low)
             at += count
         x = x[rng.permutation(n)]
+    if shape == "16-buckets":               # the top bits of every key: 1 0 .. 0 1 1, then four free bucket bits
+        low = bits - ls_topb(n) + 4
+        x = (x & U64((1 << low) - 1)) | U64(((1 << (bits - low - 1)) | 3) << low)
     m = len(x[1::7])
     x[::7][:m] = x[1::7]                    # equal keys: what the stability of a pair sort is about
+    x[3] |= U64(1 << (bits - 1))            # (neither written nor copied above) the OR of all keys is exactly `bits` wide
     return x
 
 
 def check_sort_path(row, bits, sorted_keys):
-    """from the bucket counts of the reference sort: which route the sources' constants send this input through"""
+    """from the bucket counts of the reference sort: which route the sources' constants send this input through.
+    Returns what every sort of the row leaves in the statistics: ("sort_route", the rise of "sort_bucket_declined",
+    "sort_oversized_buckets")."""
     n, shape, opts = SORT_ROWS[row]
+    general = ROUTE_HOST_HIST if n < SORT_FUSED_MIN else ROUTE_FUSED
     if n < SORT_LOCAL_MIN:
-        assert n < SORT_FUSED_MIN          # host histograms
-        return
+        assert general == ROUTE_HOST_HIST
+        return general, 0, 0
     if opts.get("sort_local") == 0:
-        assert n >= SORT_FUSED_MIN
-        return
+        assert general == ROUTE_FUSED
+        return general, 0, 0
     assert n == SORT_LOCAL_MIN and bits >= 32
-    assert int(sorted_keys[-1]) >> (bits - 1) == 1      # (key_bits = 64: the OR of all keys leaves the width at 64)
+    width = SORT_WIDTH.get(row, bits)
+    assert width == bits or bits == 64                  # (only key_bits = 64 makes the sort look at the keys' OR)
+    assert int(sorted_keys[-1]) >> (width - 1) == 1     # the OR of all keys is `width` wide: 64 stays, narrower keys narrow it
     topb = ls_topb(n)
-    assert bits >= 8 * 2 + 16 and topb <= 16
-    counts = np.bincount((sorted_keys >> U64(bits - topb)).astype(np.int64), minlength=1 << topb)
+    assert topb <= 16
+    if width < LS_MIN_BITS:
+        return general, 1, 0
+    counts = np.bincount((sorted_keys >> U64(width - topb)).astype(np.int64), minlength=1 << topb)
     big = counts > LS_CLASS_MAX
+    if shape == "16-buckets":
+        assert (counts > 0).sum() == 16 and big.sum() == 16
+        assert counts[big].sum() > n // 4               # the route gives up (and its later attempts stop at the sample)
+        return general, 1, 0
     if shape == "crowded":
         assert big.sum() == len(CROWDED) and all(big[b] for b, _ in CROWDED)
         assert big.sum() <= LS_MAX_BIG and counts[big].sum() <= n // 4       # the route does not give up
@@ -352,9 +377,16 @@ def check_sort_path(row, bits, sorted_keys):
     classes = np.unique(np.searchsorted(np.array(LS_CLASS_KPT) * 256, counts[(counts > 0) & ~big], side="left"))
     if shape == "sloped":
         assert len(classes) >= LS_FAN_MIN + 3, classes     # (well beyond the minimum: the launches go round the three streams twice)
+    return ROUTE_BUCKETS, 0, int(big.sum())
 
 
-SORT_CASES = [(row, bits) for row in SORT_ROWS for bits in (62, 64)]
+# what check_sort_path must find for the rows: (sort_route, sort_bucket_declined per sort, sort_oversized_buckets)
+SORT_STATS = {"host-hist": (1, 0, 0), "fused-hist": (2, 0, 0), "buckets": (3, 0, 0), "digit-passes": (3, 0, 0), "fan": (3, 0, 0),
+              "no-fan": (3, 0, 0), "crowded": (3, 0, len(CROWDED)), "narrow-64": (3, 0, 0), "too-narrow-64": (1, 1, 0),
+              "gives-up": (1, 1, 0)}
+
+
+SORT_CASES = [(row, bits) for row in SORT_ROWS for bits in SORT_BITS.get(row, (62, 64))]
 
 
 @pytest.mark.parametrize("row,bits", SORT_CASES)
@@ -362,7 +394,8 @@ def test_sort_shapes_oracle_only(row, bits):
     x = sort_input(row, bits, 5)
     s = np.sort(x)
     assert len(np.unique(s)) < len(s)
-    check_sort_path(row, bits, s)
+    assert check_sort_path(row, bits, s) == SORT_STATS[row]
+    assert check_sort_path(row, bits, np.sort(sort_input(row, bits, 6))) == SORT_STATS[row]     # (the stale twin's first call)
     assert len(sort_input(row, bits, 6)) == len(x) and not np.array_equal(sort_input(row, bits, 6), x)
 
 
@@ -370,8 +403,9 @@ def test_sort_shapes_oracle_only(row, bits):
 @pytest.mark.parametrize("row,bits", SORT_CASES)
 def test_sort(row, bits):
     """keys against np.sort, pairs against np.argsort(kind="stable").  A context of its own per row: the sort keeps
-    state from one call to the next (sort_skew_seen, sort_counting_skip), and a row must not inherit another row's.
-    Which route ran is not observable from the host; the CPU twin derives it from the sources' constants."""
+    state from one call to the next (SortPolicy: skew_seen, counting_skip), and a row must not inherit another row's.
+    After every sort the statistics show the route that check_sort_path derives from the sources' constants (the CPU twin
+    test_sort_shapes_oracle_only pins them to SORT_STATS)."""
     import torch
     from unikmer_amd import lib as L
     n, _, opts = SORT_ROWS[row]
@@ -380,18 +414,27 @@ def test_sort(row, bits):
     up = lambda a: torch.from_numpy(a.view(np.int64)).cuda()
     xd, expd, orderd = up(x), up(x[order]), torch.from_numpy(order.astype(np.int32)).cuda()
     od = up(sort_input(row, bits, 6))
+    route, declines, oversized = check_sort_path(row, bits, x[order])
+    assert (route, declines, oversized) == SORT_STATS[row]
     del x, order
+
+    def routed(call):
+        declined = ctx.stat("sort_bucket_declined")
+        call()
+        assert ctx.stat("sort_route") == route, (row, bits, ctx.stat("sort_route"))
+        assert ctx.stat("sort_bucket_declined") == declined + declines, (row, bits)
+        assert ctx.stat("sort_oversized_buckets") == oversized, (row, bits, ctx.stat("sort_oversized_buckets"))
 
     def keys(src, exp=None):
         w = src.clone()
         torch.cuda.synchronize()
-        ctx.sort_u64(w, bits)
+        routed(lambda: ctx.sort_u64(w, bits))
         assert exp is None or torch.equal(w, exp), (row, bits, "keys")
 
     def pairs(src, exp=None):
         w, v = src.clone(), torch.arange(n, dtype=torch.int32, device=src.device)
         torch.cuda.synchronize()
-        ctx.sort_pairs(w, v, bits)
+        routed(lambda: ctx.sort_pairs(w, v, bits))
         assert exp is None or (torch.equal(w, exp) and torch.equal(v, orderd)), (row, bits, "pairs")
 
     ctx = L.Context(0)
@@ -400,6 +443,13 @@ def test_sort(row, bits):
             for fn in (keys, pairs):
                 patterns(ctx, lambda: fn(xd, expd))
                 stale_twin(ctx, lambda: fn(od), lambda: fn(xd, expd), 1024 * MB)
+        if row == "gives-up":       # the context stays usable: evenly spread keys pass its sample and take the bucket route
+            even = np.random.default_rng(7).integers(0, 1 << bits, n, dtype=U64)
+            w = up(even)
+            declined = ctx.stat("sort_bucket_declined")
+            ctx.sort_u64(w, bits)
+            assert torch.equal(w, up(np.sort(even))), (row, bits, "even keys afterwards")
+            assert ctx.stat("sort_route") == ROUTE_BUCKETS and ctx.stat("sort_bucket_declined") == declined
     finally:
         ctx.close()
 

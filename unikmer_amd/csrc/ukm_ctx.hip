@@ -107,7 +107,7 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     if (strcmp(key, "punion_attempts") == 0) *value = c->stat_punion_attempts;
     else if (strcmp(key, "punion_flags") == 0) *value = c->stat_punion_flags;
     else if (strcmp(key, "count_window_retries") == 0) *value = c->stat_count_window_retries;
-    else if (strcmp(key, "sort_fused_hist") == 0) *value = c->stat_sort_fused_hist;
+    else if (strcmp(key, "sort_fused_hist") == 0) *value = c->sort.stat_fused_hist;
     else if (strcmp(key, "setop_part_hits") == 0) *value = c->stat_setop_part_hits;
     else if (strcmp(key, "setop_part_stale") == 0) *value = c->stat_setop_part_stale;
     else if (strcmp(key, "setop_offs_hits") == 0) *value = c->stat_setop_offs_hits;
@@ -121,6 +121,9 @@ extern "C" int ukm_ctx_get_stat(ukm_ctx *c, const char *key, unsigned long long 
     else if (strcmp(key, "pair_kernel_us") == 0) *value = c->stat_pair_kernel_us;
     else if (strcmp(key, "grep_route") == 0) *value = c->stat_grep_route;
     else if (strcmp(key, "window_route") == 0) *value = c->stat_window_route;
+    else if (strcmp(key, "sort_route") == 0) *value = c->sort.stat_route;
+    else if (strcmp(key, "sort_bucket_declined") == 0) *value = c->sort.stat_bucket_declined;
+    else if (strcmp(key, "sort_oversized_buckets") == 0) *value = c->sort.stat_oversized_buckets;
     else if (strcmp(key, "window_strip_declined") == 0) *value = c->stat_window_strip_declined;
     else if (strcmp(key, "lb_watchdogs") == 0) *value = c->stat_lb_watchdogs;
     else if (strcmp(key, "inflate_candidates") == 0) *value = c->stat_inflate_candidates;
@@ -202,7 +205,6 @@ extern "C" int ukm_ctx_destroy(ukm_ctx *c) {
     if (c->tax_pair) (void)hipFree(c->tax_pair);
     if (c->tax_top) (void)hipFree(c->tax_top);
     if (c->h_scratch) (void)hipHostFree(c->h_scratch);
-    if (c->sort_stat_dev) (void)hipFree(c->sort_stat_dev);
     if (c->part_cache.buf) (void)hipFree(c->part_cache.buf);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
@@ -213,11 +215,7 @@ extern "C" int ukm_ctx_destroy(ukm_ctx *c) {
         (void)hipStreamDestroy(c->xfer);
     }
     if (c->ev_xfer) (void)hipEventDestroy(c->ev_xfer);
-    for (int i = 0; i < 2; i++) {
-        if (c->side[i]) { (void)hipStreamSynchronize(c->side[i]); (void)hipStreamDestroy(c->side[i]); }
-        if (c->ev_side[i]) (void)hipEventDestroy(c->ev_side[i]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    c->sort.release();
     if (c->ev_comp) (void)hipEventDestroy(c->ev_comp);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/unikmer_hip.h"
+#include "ukm_sort_state.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -105,10 +106,6 @@ struct ukm_ctx {
     hipStream_t xfer = nullptr;
     hipEvent_t ev_xfer = nullptr, ev_comp = nullptr;
     bool xfer_pending = false;
-    // two more streams for launches that do not depend on each other (the bucket sort's size classes): forked from and
-    // joined to `stream` by events inside one call
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_side[2] = {nullptr, nullptr};
     // RCCL communicator of the multi-GPU exchange (ukm_comm.hip); nullptr until ukm_comm_init
     void *comm = nullptr;
     int comm_size = 0, comm_rank = 0;
@@ -251,20 +248,46 @@ struct ukm_ctx {
 
     // set once the blockIdx-ordered set-op kernel hit its watchdog on this device
     bool setop_force_ticket = false;  // = ticket_latched || option "force_ticket"
-    unsigned long long stat_sort_fused_hist = 0;  // sorts of this context that took their first histogram from the producer of the keys (ukm_count)
     bool ticket_latched = false;      // the look-back watchdog fired on this device (ukm_switch_to_tickets): stays set
     unsigned long long stat_lb_watchdogs = 0;  // times ukm_switch_to_tickets ran: a launch ladder's retry, or a chained fold's fallback
-    // set once a sort found its keys crowded into few top-16-bit buckets (ukm_sort.hip): later sorts look at a sample first
-    bool sort_skew_seen = false;
-    // buckets of the last bucket-route sort that fell back from the counting step to the digit passes (device word, bumped by
-    // ls_sort_kernel, fetched by the NEXT sort's classify kernel so that it rides on that call's read-back): keys with many
-    // copies each (k-mers of reads at coverage) make every bucket fall back, and the next calls skip the attempt
-    u64 *sort_stat_dev = nullptr;
-    bool sort_last_counting = false;
-    u64 sort_last_buckets = 0;
-    int sort_counting_skip = 0;
-    // set around the sort of the gathered oversized buckets: those keys are crowded by construction, the general passes take them
-    bool sort_general_only = false;
+
+    // The radix sort (ukm_sort.hip): what it keeps from one sort to the next and its statistics (SortPolicy, ukm_sort_state.h),
+    // and the device resources it creates on first use and ukm_ctx_destroy releases.
+    struct SortState : SortPolicy {
+        // buckets of the last bucket-route sort that fell back from the counting step to the digit passes: bumped by
+        // ls_sort_kernel, fetched and cleared by the next sort's classify kernel (SortPolicy::note_fallbacks)
+        u64 *stat_dev = nullptr;
+        // two more streams for launches that do not depend on each other (the bucket kernel's size classes): forked from and
+        // joined to the call's stream by events inside one call
+        hipStream_t side[2] = {nullptr, nullptr};
+        hipEvent_t ev_fork = nullptr, ev_side[2] = {nullptr, nullptr};
+
+        int stat_word(hipStream_t stream, u64 **out) {
+            if (!stat_dev) {
+                UKM_HIP(hipMalloc((void **)&stat_dev, 64));
+                UKM_HIP(hipMemsetAsync(stat_dev, 0, 64, stream));
+            }
+            *out = stat_dev;
+            return UKM_OK;
+        }
+        int side_streams() {
+            if (ev_fork) return UKM_OK;
+            UKM_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+            for (int i = 0; i < 2; i++) {
+                UKM_HIP(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
+                UKM_HIP(hipEventCreateWithFlags(&ev_side[i], hipEventDisableTiming));
+            }
+            return UKM_OK;
+        }
+        void release() {
+            if (stat_dev) (void)hipFree(stat_dev);
+            for (int i = 0; i < 2; i++) {
+                if (side[i]) { (void)hipStreamSynchronize(side[i]); (void)hipStreamDestroy(side[i]); }
+                if (ev_side[i]) (void)hipEventDestroy(ev_side[i]);
+            }
+            if (ev_fork) (void)hipEventDestroy(ev_fork);
+        }
+    } sort;
 };
 
 // The value of knob UKM_<NAME> for this context (see ukm_ctx::knobs): nullptr when it is not set.  The pointer stays valid
