@@ -714,6 +714,38 @@ int ukm_merge_k_ft(ukm_ctx *ctx, const uint64_t *const *keys, const uint32_t *co
 int ukm_pair_counts(ukm_ctx *ctx, const uint64_t *const *keys, const uint64_t *lens, int nstreams, int nrows,
                     uint32_t flags, uint64_t *out_counts, uint64_t *out_sizes);
 
+/* ---- which records belong to a set (new: the reference would run `count` on every record and `inter | num` the result, one
+ *      process per record): per record the number of windows, the number of windows whose value is in a sorted code set, and
+ *      the LCA of the taxids of those hits.  Reads against a host or contaminant set, contigs against a taxon-annotated
+ *      database, a marker set against a sample.
+ *      bases / rec_off as for ukm_encode_kmers (host or device, rec_off[0] == 0); canonical / circular / hashed select the
+ *      windows exactly as ukm_encode_kmers (hashed = 0) and ukm_nthash with max_hash = 0 (hashed = 1) produce them.
+ *      set_keys[n_set]: ascending, duplicates tolerated (UKM_ERR_UNSORTED otherwise, as ukm_map); set_taxids: NULL or n_set
+ *      values.  All pointers may be host or device pointers.
+ *      Outputs, exactly n_rec entries each, each may be NULL:
+ *        out_win[r] = the number of windows of record r (0 for a record shorter than k);
+ *        out_hit[r] = the number of those windows whose value is in set_keys; every window counts, repeated codes included;
+ *        out_lca[r] = 0 when out_hit[r] == 0, else the LEFT FOLD of ukm_lca's pairwise contract over the taxids of the
+ *          record's hit windows in window order, a hit's taxid being set_taxids[i] with i the FIRST index where
+ *          set_keys[i] == code.  That fold equals a closed form, which is what is computed (the argument: DESIGN.md 4.24): the
+ *          common value when all hit taxids are the same number (also an id the taxonomy does not know, also 0, also a
+ *          merged id, which stays unmapped); otherwise 0 when any hit taxid is 0 or absent after merged ids are remapped;
+ *          otherwise the LCA of the set (0 when it spans different trees).
+ *      Errors: UKM_ERR_K, UKM_ERR_ILLEGAL_BASE as the window calls give them; UKM_ERR_INVALID for a NULL ctx, for out_lca
+ *      without set_taxids, and for 2^32 or more windows, records or set codes in one call (split the records over several
+ *      calls); UKM_ERR_NO_TAXONOMY when out_lca and set_taxids are given and no taxonomy is loaded.  After an error nothing is
+ *      promised about the outputs.  n_rec == 0: UKM_OK, nothing is done.  n_set == 0: every out_hit / out_lca entry is 0,
+ *      out_win is filled.
+ *      How: the windows of all records (ukm_encode.hip) are joined against the set through its prefix
+ *      directory, and one workgroup per tile of consecutive windows folds hits, min / max raw taxid and min / max pre-order
+ *      number into per-record state: records inside a tile by plain stores, the two that cross its edges by atomics.  Context
+ *      option "map_sorted" as for ukm_map: 0 the windows look their codes up in genome order (nothing per window is written),
+ *      1 all (code, window) pairs are sorted first and one 32-bit word per window comes back; default: by the size of the set
+ *      (a threshold inherited from ukm_map).  ukm_last_kernel_ms: the lookup and reduction kernels. */
+int ukm_screen(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *rec_off, uint64_t n_rec, int k, int canonical, int circular,
+               int hashed, const uint64_t *set_keys, const uint32_t *set_taxids, uint64_t n_set, uint32_t *out_win,
+               uint32_t *out_hit, uint32_t *out_lca);
+
 /* ---- multi-GPU helper: split points of a sorted stream for prefix sharding (SURVEY.md
  *      §8(e)): cuts[g] = lower_bound(keys, splitters[g]) for g in [0, n_split). */
 int ukm_partition_points(ukm_ctx *ctx, const uint64_t *keys, uint64_t n,

@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libunikmer_hip.so")
 SOURCES = ["ukm_ctx.hip", "ukm_setops.hip", "ukm_scan.hip", "ukm_sort.hip", "ukm_encode.hip",
-           "ukm_tax.hip", "ukm_nway.hip", "ukm_kway.hip", "ukm_comm.hip", "ukm_fold.hip", "ukm_probe.hip", "ukm_probe_union.hip", "ukm_probe_ranked.hip", "ukm_place.hip", "ukm_pfold.hip", "ukm_srmerge.hip", "ukm_route.hip", "ukm_map.hip", "ukm_select.hip", "ukm_tsplit.hip", "ukm_unik.hip", "ukm_text.hip", "ukm_deflate.hip", "ukm_inflate.hip", "ukm_fastx.hip", "ukm_pairs.hip"]
-HEADERS = ["ukm_internal.h", "ukm_device.h", "ukm_kway.h", "ukm_fold.h", "ukm_probe.h", "ukm_pfold.h", "ukm_srmerge.h", "ukm_route.h", "ukm_map.h", "ukm_dir.h", "ukm_bytes.h", "ukm_huff.h", "ukm_inflate.h", "ukm_setop_part.h", "ukm_setop_tile.h", "ukm_setop_kernels.h", "ukm_setop_order.h", "ukm_win_common.h", "ukm_win_kernels.h", "ukm_win_minimizer.h", "ukm_pairs.h", "ukm_sort_state.h", "ukm_sort_plan.h", "ukm_sort_kernels.h", "ukm_sort_buckets.h", os.path.join("..", "..", "include", "unikmer_hip.h")]
+           "ukm_tax.hip", "ukm_nway.hip", "ukm_kway.hip", "ukm_comm.hip", "ukm_fold.hip", "ukm_probe.hip", "ukm_probe_union.hip", "ukm_probe_ranked.hip", "ukm_place.hip", "ukm_pfold.hip", "ukm_srmerge.hip", "ukm_route.hip", "ukm_map.hip", "ukm_select.hip", "ukm_tsplit.hip", "ukm_unik.hip", "ukm_text.hip", "ukm_deflate.hip", "ukm_inflate.hip", "ukm_fastx.hip", "ukm_pairs.hip", "ukm_screen.hip"]
+HEADERS = ["ukm_internal.h", "ukm_device.h", "ukm_kway.h", "ukm_fold.h", "ukm_probe.h", "ukm_pfold.h", "ukm_srmerge.h", "ukm_route.h", "ukm_map.h", "ukm_dir.h", "ukm_bytes.h", "ukm_huff.h", "ukm_inflate.h", "ukm_setop_part.h", "ukm_setop_tile.h", "ukm_setop_kernels.h", "ukm_setop_order.h", "ukm_win_common.h", "ukm_win_kernels.h", "ukm_win_minimizer.h", "ukm_pairs.h", "ukm_screen.h", "ukm_sort_state.h", "ukm_sort_plan.h", "ukm_sort_kernels.h", "ukm_sort_buckets.h", os.path.join("..", "..", "include", "unikmer_hip.h")]
 # The test library (tests/test_gpu_lb_retry.py): the sources that include the decoupled look-back, compiled once more with
 # the watchdog's injection seam of ukm_device.h (UKM_LB_TEST_TIMEOUT) into objects of their own, and linked with the product
 # objects of all other sources.  The product library never sees the macro.

@@ -421,9 +421,6 @@ __global__ void expand_kernel(const u64 *hk, const u32 *hv, u64 n, const u64 *wi
 // ---- host steps -------------------------------------------------------------------------------------------------------
 unsigned blocks_for(u64 n) { return (unsigned)((n + NT - 1) / NT); }
 
-// log2 of the codes per prefix of the directory (developer knob; 1 / 2 / 3 measured: DESIGN.md 4.14)
-int dir_slack(const ukm_ctx *c) { return ukm_env_int(c, "UKM_MAP_DIR_SLACK", DIR_SLACK_DEFAULT); }
-
 // flag: n rounded up to whole tiles (the kernels read and write 8-byte words)
 size_t flag_bytes(u64 n) { return (size_t)((n + TILE - 1) / TILE * TILE + 8); }
 
@@ -456,44 +453,45 @@ int run_join(ukm_ctx *c, const u64 *w, const u32 *wi, u64 n, const Dir &d, u8 *f
     return UKM_OK;
 }
 
+}  // namespace
+
+// ---- host steps shared with ukm_screen.hip (declared in ukm_map.h) -------------------------------------------------------
+// log2 of the codes per prefix of the directory (developer knob; 1 / 2 / 3 measured: DESIGN.md 4.14)
+int ukm_map_dir_slack(const ukm_ctx *c) { return ukm_env_int(c, "UKM_MAP_DIR_SLACK", DIR_SLACK_DEFAULT); }
+
 // Route policy: a window's lookup in genome order is a gather into the sorted array.  While the array
 // (and its directory) stays near the caches that is the cheapest membership there is; against an array of hundreds of MB
 // every lookup is an HBM row, and sorting the (code, window) pairs first -- neighbouring lanes then read neighbouring
 // entries -- costs less than the gathers it saves.  Option "map_sorted" 0 / 1 forces either.
 // Measured at 1e8 windows: ukm_map 1e7 codes 5.6 (genome order) against 6.1 ms (sorted), 1e8 codes 9.6 against 7.3;
-// ukm_locate, whose join also compacts, 1e7 queries 5.7 against 4.9.
-constexpr u64 MAP_SORTED_MIN_KEYS = 1ull << 24, LOCATE_SORTED_MIN_KEYS = 1ull << 23;
-bool sorted_route(const ukm_ctx *c, u64 n_keys, u64 min_keys) {
+// ukm_locate, whose join also compacts, 1e7 queries 5.7 against 4.9.  (The thresholds: ukm_map.h.)
+bool ukm_map_sorted_route(const ukm_ctx *c, u64 n_keys, u64 min_keys) {
     const char *e = ukm_env(c, "UKM_MAP_SORTED");
     if (e && *e) return e[0] == '1';
     return n_keys >= min_keys;
 }
 // (w, wi) = every window and its index, sorted by code (stably: equal codes by window)
-int sort_windows(ukm_ctx *c, u64 *w, u64 n, int key_bits, u32 **wi) {
+int ukm_dev_sort_windows(ukm_ctx *c, u64 *w, u64 n, int key_bits, u32 **wi) {
     UKM_TRY(ws_alloc_t(c, n, wi));
     hipLaunchKernelGGL(iota_u32_kernel, dim3(std::min(blocks_for(n), (unsigned)c->num_cu * 16u)), dim3(NT), 0, c->stream, *wi, n);
     return ukm_dev_sort(c, w, *wi, n, key_bits);
 }
 
-// what both entry points do first: stage the records, produce the windows
-struct Windows {
-    const u64 *rec_off = nullptr;  // device
-    const u64 *win_off = nullptr;  // device, [n_rec + 1]
-    u64 *w = nullptr;
-    u64 n = 0;
-};
-int make_windows(ukm_ctx *c, const char *name, const u8 *bases, const u64 *rec_off, u64 n_rec, int k, int circular, int hashed,
-                 Windows *W) {
+// what every entry point does first: stage the records, produce the windows
+int ukm_dev_make_windows(ukm_ctx *c, const char *name, const u8 *bases, const u64 *rec_off, u64 n_rec, int k, int canonical, int circular,
+                         int hashed, MapWindows *W) {
     u64 total_bases = 0;
     const u8 *b = nullptr;
     UKM_TRY(ukm_dev_stage_records(c, name, bases, rec_off, n_rec, &W->rec_off, &b, &total_bases));
     UKM_TRY(ws_alloc_t(c, (size_t)total_bases + 1, &W->w));
-    UKM_TRY(ukm_dev_windows(c, hashed != 0, b, W->rec_off, n_rec, k, 1, circular, W->w, total_bases + 1, &W->n, total_bases, &W->win_off));
+    UKM_TRY(ukm_dev_windows(c, hashed != 0, b, W->rec_off, n_rec, k, canonical, circular, W->w, total_bases + 1, &W->n, total_bases, &W->win_off));
     if (W->n >= (1ull << 32))
         UKM_FAIL(UKM_ERR_INVALID, "%s: %llu windows in one call; the limit is 2^32 - 1 (window indices are the 32-bit payload of the pair sort): "
                  "split the records over several calls", name, (unsigned long long)W->n);
     return UKM_OK;
 }
+
+namespace {
 
 int check_args(const char *name, const void *ctx, const void *n_out, const void *bases, const void *rec_off, u64 n_rec, int k, int hashed) {
     if (!ctx || !n_out || (n_rec && (!rec_off || !bases))) UKM_FAIL(UKM_ERR_INVALID, "%s: NULL argument", name);
@@ -526,8 +524,8 @@ extern "C" int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *re
             ukm_out_resize(ctx, out_pos, n * sizeof(u64));
         };
         const int r = [&]() -> int {
-        Windows W;
-        UKM_TRY(make_windows(ctx, name, bases, rec_off, n_rec, k, circular, hashed, &W));  // (also without queries: an illegal base is an error)
+        MapWindows W;
+        UKM_TRY(ukm_dev_make_windows(ctx, name, bases, rec_off, n_rec, k, 1, circular, hashed, &W));  // (also without queries: an illegal base is an error)
         if (W.n == 0 || nq == 0) return UKM_OK;
         // the queries, sorted stably with their indices (all 64 bits: they are the caller's, not ours)
         u64 *qs = nullptr;
@@ -538,7 +536,7 @@ extern "C" int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *re
         hipLaunchKernelGGL(iota_u32_kernel, dim3(std::min(blocks_for(nq), (unsigned)ctx->num_cu * 16u)), dim3(NT), 0, ctx->stream, qi, nq);
         UKM_TRY(ukm_dev_sort(ctx, qs, qi, nq, 64));
         Dir d;
-        UKM_TRY(build_dir(ctx, qs, nq, hashed ? 64 : 2 * k, dir_slack(ctx), &d));
+        UKM_TRY(build_dir(ctx, qs, nq, hashed ? 64 : 2 * k, ukm_map_dir_slack(ctx), &d));
         // hits in window order.  The caller's capacity bounds the first attempt's buffers (a host that asks for a few
         // positions pays for a few); more hits than that: the exact number goes back with UKM_ERR_CAPACITY
         const u64 hcap = std::min<u64>(W.n, out_cap);
@@ -548,7 +546,7 @@ extern "C" int ukm_locate(ukm_ctx *ctx, const uint8_t *bases, const uint64_t *re
         UKM_TRY(ws_alloc_t(ctx, hcap + 1, &hv));
         u64 nh = 0;
         u32 *wi = nullptr;  // (sorted route: the hits then come by code, a code's windows ascending; the sort below keeps that)
-        if (sorted_route(ctx, nq, LOCATE_SORTED_MIN_KEYS)) UKM_TRY(sort_windows(ctx, W.w, W.n, hashed ? 64 : 2 * k, &wi));
+        if (ukm_map_sorted_route(ctx, nq, LOCATE_SORTED_MIN_KEYS)) UKM_TRY(ukm_dev_sort_windows(ctx, W.w, W.n, hashed ? 64 : 2 * k, &wi));
         UKM_TRY(run_join(ctx, W.w, wi, W.n, d, nullptr, qi, true, hk, hv, hcap, &nh));
         *n_out = nh;
         if (nh > out_cap)
@@ -617,8 +615,8 @@ int map_regions(ukm_ctx *ctx, const char *name, const u8 *bases, const u64 *rec_
     bool sorted = true, strict = true;
     UKM_TRY(ukm_dev_check_sorted(ctx, set, n_set, &sorted, &strict));
     if (!sorted) UKM_FAIL(UKM_ERR_UNSORTED, "%s: the code set is not sorted", name);
-    Windows W;  // (circular: the L circular windows of every record, the ones map.go:222-226 counts multiplicity among)
-    UKM_TRY(make_windows(ctx, name, bases, rec_off, n_rec, k, o.circular, hashed, &W));
+    MapWindows W;  // (circular: the L circular windows of every record, the ones map.go:222-226 counts multiplicity among)
+    UKM_TRY(ukm_dev_make_windows(ctx, name, bases, rec_off, n_rec, k, 1, o.circular, hashed, &W));
     if (W.n == 0 || n_set == 0) return UKM_OK;
     const bool plain = !o.circular && o.max_gap_size == 0;
     if (!plain && !o.circular && W.n >= (1ull << 31))
@@ -626,7 +624,7 @@ int map_regions(ukm_ctx *ctx, const char *name, const u8 *bases, const u64 *rec_
                  "look-back word): split the records over several calls", name, (unsigned long long)W.n);
     const int key_bits = hashed ? 64 : 2 * k;
     Dir d;
-    UKM_TRY(build_dir(ctx, set, n_set, key_bits, dir_slack(ctx), &d));
+    UKM_TRY(build_dir(ctx, set, n_set, key_bits, ukm_map_dir_slack(ctx), &d));
     u8 *flag = nullptr;
     UKM_TRY(ws_alloc_t(ctx, flag_bytes(W.n), &flag));
     Genomes G = {nullptr, n_genome};
@@ -636,10 +634,10 @@ int map_regions(ukm_ctx *ctx, const char *name, const u8 *bases, const u64 *rec_
         hipLaunchKernelGGL(genome_windows_kernel, dim3(blocks_for(n_genome + 1)), dim3(NT), 0, ctx->stream, goff, W.win_off, n_genome, gwin);
         G.gwin = gwin;
     }
-    if (sorted_route(ctx, n_set, MAP_SORTED_MIN_KEYS)) {
+    if (ukm_map_sorted_route(ctx, n_set, MAP_SORTED_MIN_KEYS)) {
         // every (code, window) pair sorted, the set looked up in sorted order, the flags scattered back
         u32 *wi = nullptr;
-        UKM_TRY(sort_windows(ctx, W.w, W.n, key_bits, &wi));
+        UKM_TRY(ukm_dev_sort_windows(ctx, W.w, W.n, key_bits, &wi));
         UKM_HIP(hipMemsetAsync(flag, 0, flag_bytes(W.n), ctx->stream));
         (void)hipEventRecord(ctx->ev_k0, ctx->stream);
         hipLaunchKernelGGL(sorted_classify_kernel, dim3(blocks_for(W.n)), dim3(NT), 0, ctx->stream, W.w, wi, W.n, d, G, allow_multi, flag);

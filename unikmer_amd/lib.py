@@ -55,6 +55,7 @@ SYMBOLS = [
     "ukm_fastx",
     "ukm_setop2_multi",
     "ukm_pair_counts",
+    "ukm_screen",
 ]
 
 
@@ -185,6 +186,7 @@ def load():
     L.ukm_locate.argtypes = [vp, vp, vp, u64, i32, i32, i32, vp, u64, vp, vp, vp, u64, pu64]
     L.ukm_map.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, vp, u64, i32, u64, vp, vp, vp, u64, pu64]
     L.ukm_map_gapped.argtypes = [vp, vp, vp, u64, vp, u64, i32, i32, i32, vp, u64, i32, u64, u64, u64, vp, vp, vp, u64, pu64]
+    L.ukm_screen.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, u64, vp, vp, vp]
     L.ukm_grep.argtypes = [vp, vp, vp, u32, u64, i32, vp, vp, u64, u32, vp, vp, u64, pu64]
     L.ukm_filter.argtypes = [vp, vp, vp, u64, i32, i32, i32, i32, i32, u32, vp, vp, u64, pu64]
     L.ukm_sample.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, u64, pu64]
@@ -650,6 +652,35 @@ class Context:
                                                                     ps, ns, int(allow_multi), int(min_len), int(max_gap_size),
                                                                     int(max_gap_num), o[0], o[1], o[2], cap, C.byref(n)),
                             bases, (np.uint32, np.uint64, np.uint64), out_cap, outs)
+
+    # ---- which records belong to a set ----
+    def screen(self, bases, rec_off, k, set_keys, set_taxids=None, canonical=True, circular=False, hashed=False, lca=None, outs=None):
+        """Per record: (win, hit, lca) = its number of windows, the number of them whose value is in the sorted `set_keys`
+        (every window counts), and the LCA of the hits' taxids (include/unikmer_hip.h: ukm_screen; 0 without a hit; needs a
+        loaded taxonomy).  lca defaults to `set_taxids is not None`; without it the third value is None.  The windows are
+        those of encode_kmers (hashed=False) / nthash (hashed=True) with the same canonical / circular.  outs: the caller's
+        (win, hit, lca) arrays of n_rec uint32 each; an entry that is None is not computed and comes back as None."""
+        pb, _, k1 = _ptr(bases, np.uint8)
+        poff, noff, k2 = _ptr(rec_off, np.uint64)
+        ps, ns, k3 = _ptr(set_keys, np.uint64)
+        pt, nt, k4 = _ptr(set_taxids, np.uint32)
+        n_rec = max(noff - 1, 0)
+        if set_taxids is not None and nt != ns:
+            raise ValueError("screen: set_taxids must be as long as set_keys")
+        if lca is None:
+            lca = set_taxids is not None
+        if lca and set_taxids is None:
+            raise ValueError("screen: lca needs set_taxids")
+        if outs is None:
+            outs = (_empty_like_kind(bases, n_rec, np.uint32), _empty_like_kind(bases, n_rec, np.uint32),
+                    _empty_like_kind(bases, n_rec, np.uint32) if lca else None)
+        elif len(outs) != 3 or any(o is not None and _ptr(o, np.uint32)[1] < n_rec for o in outs):
+            raise ValueError("screen: outs must be (win, hit, lca) of at least n_rec items each (or None)")
+        po = [None if o is None else (_ptr(o, np.uint32)[0] if n_rec else None) for o in outs]
+        if po[2] is not None and ns == 0:
+            pt = None   # (an empty set has no taxids to point at: every lca is 0)
+        _check(self.L.ukm_screen(self.h, pb, poff, n_rec, int(k), int(canonical), int(circular), int(hashed), ps, pt, ns, po[0], po[1], po[2]))
+        return tuple(None if o is None else o[:n_rec] for o in outs)
 
     # ---- record selection (grep / filter / sample): kept records in input order, taxids copied ----
     def _select(self, call, keys, taxids, bound, out, out_taxids):
